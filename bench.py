@@ -15,7 +15,9 @@ synthetic replay batch that is already resident in HBM.  Weak scaling: every ran
 (low_dim 7, arm-prediction loss, per-sample crop bounds), both resident on every GPU; one step = each agent updating on 4
 independently SE(3)-perturbed copies of its 16 replay samples (4 update() calls per agent, 128 voxel grids per step).
 
-Rank 0 prints ONE JSON line (metric/value/... + `roofline` for the dominant kernel + `cpu_baseline`).
+Rank 0 prints ONE JSON line (metric/value/... + `roofline` for the dominant kernel + `cpu_baseline`).  With --dump-outputs DIR it also
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs): the same arguments give the same inputs, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -65,6 +67,8 @@ def main():
                          'two batches resident in HBM.  Without the flag the same measurement is reported beside the headline '
                          'as `replay_stream` (offline_train_runner.py:136-143: Sample time + Step time)')
     ap.add_argument('--replay-rows', type=int, default=96, help='distinct synthetic transitions in the replay store of --replay-stream')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed as DIR/<name>.npy (see dump_outputs)')
     a = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -127,6 +131,7 @@ def main():
 
     streams = [None]                  # [list of one DeviceBatchStream per agent] while a replay-stream region is measured
     sample_s = [0.0]
+    last_out = [None] * len(agents)   # what each agent's latest update() returned (--dump-outputs)
 
     def step():
         i = counter[0]
@@ -142,6 +147,7 @@ def main():
             for _ in range(a.aug_copies):          # every call draws a fresh SE(3) perturbation of the same replay samples
                 out = ag.update(i, dict(batch))
                 loss = float(out['total_losses'])  # the runner's .item() (device sync every update)
+                last_out[ai] = out
         return loss
 
     def open_streams():
@@ -228,6 +234,8 @@ def main():
     for ar in arenas:
         ar.timing = world > 1         # N > 1: events around the bucketed gradient exchange of the timed region (flat_params.py)
     dt, loss, agg_head = measure(headline_mode, a.steps, 1 if a.replay_stream else 0, only={dom_label, 'voxelize'}, stream=a.replay_stream)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, agents, last_out)      # before any later measurement steps the agents again
     exchange = None
     if world > 1:
         exchange = {'backend': dist.get_backend(), 'world_size_observed': dist.get_world_size(), 'rank': rank,
@@ -423,6 +431,38 @@ def main():
     if world > 1:
         dist.barrier()                   # rank 0 did the rank-0-only extras; leave together
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20       # elements kept of a larger array (a seeded sample): 4 MB per array, well under 64 MB per dump
+
+
+def dump_outputs(out_dir, agents, last_out):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (float32; integer results as float64), so that two
+    builds run with the same arguments -- hence on the same inputs -- can be compared output for output.  Per agent (prefix agentN_
+    with the twin agents): update()'s return value `total_losses`, the loss terms of its summaries, the predicted translation voxel
+    and rotation / gripper / collision classes, the translation Q-values of the first sample, and the parameters and their gradients
+    after the step.  An array of more than DUMP_SAMPLE elements is written as the same seeded sample of DUMP_SAMPLE of them."""
+    import numpy as np
+    arrays = {}
+    for ai, (ag, out) in enumerate(zip(agents, last_out)):
+        pre = 'agent%d_' % ai if len(agents) > 1 else ''
+        qa = ag._pose_agent._qattention_agents[0]
+        arrays[pre + 'total_losses'] = out['total_losses']
+        arrays.update((pre + k.replace('/', '_'), v) for k, v in qa._summaries.items() if k.startswith('losses/'))
+        arrays[pre + 'pred_trans_voxel'], arrays[pre + 'pred_rot_grip_collision'] = qa._last_pred
+        arrays[pre + 'q_trans_sample0'] = qa._vis_q_trans0
+        arrays[pre + 'params'], arrays[pre + 'grads'] = qa._arena.flat_w, qa._arena.flat_g
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        x = t.cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), x)
+        total += x.nbytes
+    assert total <= 64 << 20, total
 
 
 # HBM bytes per launch of the dominant kernel: read from the NEWEST committed PMC passes of this command at configs[1]

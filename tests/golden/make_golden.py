@@ -659,6 +659,57 @@ def f12_clip_text():
         float(feat.abs().max()), float(emb.abs().max()), int((tokens != 0).sum(1).max())))
 
 
+def f12b_clip_bpe_subset():
+    """The part of CLIP's BPE merge list (bpe_simple_vocab_16e6.txt.gz, as the reference tokenizer reads it) that the F12 sentences
+    touch, with the ranks it has there: every merge that is a candidate (an adjacent pair with a rank) at some step of the BPE of
+    those words, and the merge behind every output token.  BPE merges the lowest-ranked candidate, so a merge that is never a
+    candidate cannot change the outcome: the subset at its ranks, every other rank taken by a pair that cannot occur, gives the
+    reference's token ids (tests/test_clip_tokenizer_cpu.py) without the 1.3 MB vocabulary."""
+    import regex
+    import types
+    stub_modules()
+    sys.modules['ftfy'].fix_text = lambda t: t
+    if 'ref_clip_pkg' not in sys.modules:
+        pkg = types.ModuleType('ref_clip_pkg')
+        pkg.__path__ = [os.path.join(REF, 'peract', 'helpers', 'clip', 'core')]
+        sys.modules['ref_clip_pkg'] = pkg
+    st = importlib.import_module('ref_clip_pkg.simple_tokenizer')
+    tok = st.SimpleTokenizer()
+    ranks, n_merges = tok.bpe_ranks, len(tok.bpe_ranks)
+    keep = set()
+    for text in F12_SENTENCES:
+        for t in regex.findall(tok.pat, st.whitespace_clean(st.basic_clean(text)).lower()):
+            t = ''.join(tok.byte_encoder[b] for b in t.encode('utf-8'))
+            word = list(t[:-1]) + [t[-1] + '</w>']
+            while len(word) > 1:
+                cands = [(ranks[p], p) for p in zip(word[:-1], word[1:]) if p in ranks]
+                if not cands:
+                    break
+                keep.update(r for r, _ in cands)
+                a, b = min(cands)[1]
+                merged, i = [], 0
+                while i < len(word):
+                    if i < len(word) - 1 and (word[i], word[i + 1]) == (a, b):
+                        merged.append(a + b)
+                        i += 2
+                    else:
+                        merged.append(word[i])
+                        i += 1
+                word = merged
+            assert ' '.join(word) == tok.bpe(t), (t, word)
+            keep.update(tok.encoder[w] - 512 for w in word if 512 <= tok.encoder[w] < 512 + n_merges)
+    by_rank = {r: m for m, r in ranks.items()}
+    rank = np.array(sorted(keep), dtype=np.int32)
+    arrs = dict(rank=rank, first=np.array([by_rank[int(r)][0] for r in rank]), second=np.array([by_rank[int(r)][1] for r in rank]),
+                n_merges=np.int64(n_merges))
+    from tests.test_clip_tokenizer_cpu import merges_from_subset
+    from voxactb_amd.helpers.clip_text import SimpleTokenizer
+    want = np.load(os.path.join(HERE, 'f12_clip_text.npz'), allow_pickle=False)['tokens']
+    assert np.array_equal(SimpleTokenizer(merges=merges_from_subset(arrs)).tokenize(F12_SENTENCES).numpy(), want)
+    save('f12b_clip_bpe_subset', **arrs)
+    print('f12b: %d of %d merges' % (len(rank), n_merges))
+
+
 # ----------------------------------------------------------------------------- F6 / F9: agent-level
 def stub_modules():
     for name in ['torchvision', 'torchvision.transforms', 'pytorch3d', 'pytorch3d.transforms', 'pyrender',
@@ -1331,6 +1382,7 @@ SECTIONS = {
     'f11c1': lambda: encoder2_fixture('f11_encoder_2robots_c1', CFG_C1),
     'f11c2': lambda: encoder2_fixture('f11c2_encoder_2robots_c2_digest', CFG_C2, digest=True),
     'f12': f12_clip_text,
+    'f12b': f12b_clip_bpe_subset,
     'f13': f13_update_traces_2robots,
     'f14': f14_act_2robots,
     'f6': f6_update_traces,

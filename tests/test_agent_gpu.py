@@ -140,7 +140,7 @@ def test_checkpoint_roundtrip_act_and_summaries(golden, tmp_path):
         assert n1.replace('.module', '') == n2 and torch.equal(p1.data, p2.data)
 
 
-def test_se3_augmentation_path_runs(golden):
+def test_se3_augmentation_path_runs(golden, tmp_path):
     g = golden('f6_update_traces')
     agent, cfg = make_agent(g, 'a')
     qa = agent._pose_agent._qattention_agents[0]
@@ -166,7 +166,7 @@ def test_se3_augmentation_path_runs(golden):
     agent.update(4, raw_batch(g, 'a', 14))
     agent.update(5, bad)
     with pytest.raises(Exception, match='Failing to perturb'):
-        agent.save_weights('/tmp')
+        agent.save_weights(str(tmp_path))
 
 
 def test_training_curve_default_precision_tracks_exact_fp32(golden):

@@ -9,6 +9,15 @@ def T(a):
     return torch.from_numpy(np.asarray(a))
 
 
+EPS32 = float(torch.finfo(torch.float32).eps)
+
+
+def ulp_close(a, b, ulps=2):
+    """equal to within `ulps` float32 rounding steps of the tensor's largest magnitude.  A fixture is bit-exact on the CPU that
+    generated it; other x86 CPUs take other MKL kernels (sgemm, the vector sqrt ATen calls), which can round the last bit differently."""
+    return float((a - b).abs().max()) <= ulps * EPS32 * float(b.abs().max())
+
+
 def test_voxel_kats(golden):
     g = golden('f1_voxel_kats')
     out = ovox.voxelize(T(g['kat_coords']), T(g['kat_feats']), T(g['kat_bounds']), int(g['kat_V']))
@@ -66,6 +75,11 @@ def _check_encoder(g, cams, with_grads=True):
         grads = torch.autograd.grad(total, [P[n] for n in names])
         ref_norms = T(g['grad_norms'])
         for n, gr, rn in zip(names, grads, ref_norms):
+            if n == 'trans_decoder.conv3d.bias':
+                # this bias shifts every translation logit alike: its exact gradient is 0 (softmax - one-hot sums to 0), and both runs
+                # hold the float32 rounding of a sum over V^3 voxels -- held to that bound, not to the other run's rounding
+                assert float(gr.norm()) <= EPS32 * V ** 1.5 and float(rn) <= EPS32 * V ** 1.5, (n, float(gr.norm()), float(rn))
+                continue
             assert abs(float(gr.norm()) - float(rn)) <= 2e-3 * float(rn) + 1e-6, n
             key = 'grad__' + n
             if key in g.files:
@@ -88,7 +102,7 @@ def test_lamb(golden):
         m, v = torch.zeros_like(w), torch.zeros_like(w)
         for step in range(3):
             w, m, v, _ = oagent.lamb_step(w, T(g['%s_g%d' % (name, step)]), m, v)
-            assert torch.equal(w, T(g[name + '_w'])[step]), (name, step)
+            assert ulp_close(w, T(g[name + '_w'])[step]), (name, step)
 
 
 def test_se3_fixture(golden):
@@ -103,7 +117,7 @@ def test_se3_fixture(golden):
             ti, ri, pp, ok = ose3.augment(*args, T(g[tag + '_shift_unit'])[a], T(g[tag + '_rpy_steps'])[a], [0.125] * 3, 5, 100, 5, layer=layer)
             assert ok == (a == used - 1), (tag, a)
         assert torch.equal(ti.long(), T(g[tag + '_trans_idx']).long()) and torch.equal(ri.long(), T(g[tag + '_rot_grip_idx']).long())
-        assert torch.equal(pp[0], T(g[tag + '_pcd0_out'])) and torch.equal(pp[1], T(g[tag + '_pcd1_out']))
+        assert ulp_close(pp[0], T(g[tag + '_pcd0_out'])) and ulp_close(pp[1], T(g[tag + '_pcd1_out']))
         # rigid: pairwise distances preserved
         B = pcd[0].shape[0]
         a, b = pcd[0].reshape(B, 3, -1), pp[0].reshape(B, 3, -1)
@@ -119,7 +133,7 @@ def test_se3_fixture(golden):
         assert (r[3] and l[3]) == (a == used - 1)
     assert torch.equal(r[0].long(), T(g['t_trans_idx_right']).long()) and torch.equal(r[1].long(), T(g['t_rot_grip_idx_right']).long())
     assert torch.equal(l[0].long(), T(g['t_trans_idx_left']).long()) and torch.equal(l[1].long(), T(g['t_rot_grip_idx_left']).long())
-    assert torch.equal(r[2][0], T(g['t_pcd0_out']))
+    assert ulp_close(r[2][0], T(g['t_pcd0_out']))
 
 
 def test_depth_to_point_cloud_fixture(golden):
