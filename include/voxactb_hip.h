@@ -82,7 +82,15 @@ int vxb_voxelize_depth_f32(const float* const* depth_src, const float* const* fe
  * FeedForward, lang_preprocess (perceiver_lang_io.py:80-132, :417).
  *   C[z] (+)= act(alpha * A[z] @ B[z] + bias) (+ residual[z]),  z in [0,batch): offsets (z/H)*b?1 + (z%H)*b?2
  * A(m,k) at A[m*sAm + k*sAk], B(k,n) at B[k*sBk + n*sBn]; one stride of each operand must be 1 and the
- * other a multiple of 4 (16-byte loads).  act: 0 none, 1 LeakyReLU(slope). */
+ * other a multiple of 4 (16-byte loads).  act: an activation code (below).
+ *
+ * Activation codes (`int act` of every activating forward entry, and of the *_act_f32 backward entries):
+ *   0 none, 1 LeakyReLU(slope) -- ReLU is code 1 with slope 0 --, 2 tanh (ocml tanhf).  Any other value
+ *   returns -1 (bad argument).  The backward entries take the activation's SAVED OUTPUT y and multiply the incoming gradient
+ *   by the derivative read from it: y > 0 ? 1 : slope for code 1 (PyTorch's ReLU / LeakyReLU backward gate on the output
+ *   the same way), 1 - y * y for code 2 (PyTorch's tanh_backward), 1 for code 0.  The fp16 paths that take the operand
+ *   scale of a data gradient while writing it (dst_scale, du_scale) take it after this factor.  The backward entries without
+ *   `_act` in their name (ABI 4 and earlier) are their *_act_f32 sibling with act = 1. */
 int vxb_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
                  int M, int N, int K, int64_t sAm, int64_t sAk, int64_t sBk, int64_t sBn, int64_t ldc,
                  int batch, int H, int64_t bA1, int64_t bA2, int64_t bB1, int64_t bB2, int64_t bC1,
@@ -111,6 +119,8 @@ int vxb_conv3d_wgrad_f32(const float* src0, const float* src1, int C0, int C1, i
  * positions i that clamp to j; optionally times LeakyReLU'(lrelu_of[b,j,c]) (the producer's activation). */
 int vxb_fold_pad_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
                      int C, int pad, int accumulate, float slope, vxb_stream_t stream);
+int vxb_fold_pad_act_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S, int C,
+                         int pad, int accumulate, int act, float slope, vxb_stream_t stream);
 /* Rigid transform of a channels-first point cloud [B, 3, n] (apply_se3_augmentation / perturb_se3,
  * peract/voxel/augmentation.py:36-57): dst[b, :, i] = (src[b, :, i] - t_b) R_b + c_b with points as ROW vectors;
  * xf [B][15] = R_b (row-major 3x3), t_b (gripper position), c_b (new, clamped centre). */
@@ -319,6 +329,10 @@ int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, const void* 
                              float* dst1, const float* y0, const float* y1, int acc0, int acc1, float slope,
                              const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
                              vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_act_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
+                                 float* dst1, const float* y0, const float* y1, int acc0, int acc1, int act, float slope,
+                                 const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
+                                 vxb_stream_t stream);
 /* workgroups of that launch = words of scale_ws needed when dst_scale is asked for; dst_colsum ([64], accumulated: column sums of
  * dst0 as written = the bias gradient of the conv whose activation y0 is; N = 64) needs colsum_ws of 64 * (that + 64) floats */
 size_t vxb_conv3_dgrad_fold_blocks(int B, int S, int N);
@@ -327,28 +341,41 @@ size_t vxb_conv3_dgrad_fold_blocks(int B, int S, int N);
  * gradient, which only feeds the weight gradient of the 1x1x1 input conv (a leaf of the backward pass). */
 int vxb_conv3_dgrad_fold_f16_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
                                  int acc, float slope, const float* scale, vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_f16_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
+                                     int acc, int act, float slope, const float* scale, vxb_stream_t stream);
 /* ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_dgrad_fold_f16x2_wg_f32): wfrag_f16_wg = ops.halo_wfrag_x2_wg; S even,
  * scale required. */
 int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
                                  int acc, float slope, const float* scale, vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_f16_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst,
+                                        const float* y, int acc, int act, float slope, const float* scale, vxb_stream_t stream);
 /* ... on TWO fp16 products per term for a block that propagates (the d(u0) half): dy * scale[0] as an fp16 hi + lo pair, the weights
  * as one fp16 value (wfrag_f16x2: single-plane fragment order of the fp16 [64][27 C0] matrix); optional by-products as in
  * vxb_conv3_dgrad_fold_f32 (dst_scale [2] + scale_ws, dst_colsum [64] ACCUMULATED + colsum_ws). */
 int vxb_conv3_dgrad_fold_f16x2_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
                                    int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
                                    float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_f16x2_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst,
+                                       const float* y, int acc, int act, float slope, const float* scale, float* dst_scale,
+                                       float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
 /* ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_halo_ss3d_wg_bf16x3_f32): wfrag_f16x2_wg = ops.halo_wfrag_x2_wg,
  * the 36 transformed taps rounded to fp16 after the transform; S even.  dy * scale[0] / 2 is carried (the transformed operand is a sum
  * of two values).  Against the direct entry: ~1e-6 of the largest output (tests/test_halo_winograd_gpu.py). */
 int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst, const float* y,
                                    int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
                                    float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_f16x2_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
+                                          const float* y, int acc, int act, float slope, const float* scale, float* dst_scale,
+                                          float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
 /* ... when that block is the data gradient of a 1x1x1 conv's output y = lrelu(W_in x + b_in) whose input x [B, S^3, 10] is a detached
  * tensor (the input conv of the Q-function, perceiver_lang_io.py:357; agent :100): it only feeds dW_in [64][10] / db_in [64], so it is
  * not stored -- the epilogue multiplies it with LeakyReLU'(y) and x, and the sums are ACCUMULATED into dW / db.
  * ws: 704 * (vxb_conv3_dgrad_fold_blocks(B, S, 64) + 512) floats. */
 int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y, const float* x,
                                       float slope, const float* scale, float* ws, float* dW, float* db, vxb_stream_t stream);
+int vxb_conv3_dgrad_fold_f16_wgin_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
+                                          const float* x, int act, float slope, const float* scale, float* ws, float* dW,
+                                          float* db, vxb_stream_t stream);
 /* LDS-halo weight gradient of the same 3x3x3 stride-1 convs (contract of vxb_conv3d_wgrad_f32 with kext = 3, stride = 1;
  * the z slices of part[z][K][N] are runs of 128-voxel tiles, 2x8x8 or 4x4x8 -- chosen by the voxels wasted on the
  * edge of an S_out^3 grid; vxb_conv3_wgrad_halo_tiles returns their number).  C0, C1 % 16 == 0, N % 64 == 0; d2s needs
@@ -395,8 +422,12 @@ int vxb_polyphase_weights_bwd_f32(const float* dWeff, const float* L, float* dW,
 /* 1x1x1 input conv 10 -> 64 + LeakyReLU (perceiver_lang_io.py:357) and its parameter gradients (ACCUMULATED). */
 int vxb_pointwise_fwd_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
                           int Cout, float slope, vxb_stream_t stream);
+int vxb_pointwise_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin, int Cout,
+                              int act, float slope, vxb_stream_t stream);
 int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
                             int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream);
+int vxb_pointwise_wgrad_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
+                                int64_t nvox, int Cin, int Cout, int act, float slope, vxb_stream_t stream);
 
 /* 3x3x3 conv with one output channel = trans_decoder (perceiver_lang_io.py:465): forward, data gradient
  * (replicate adjoint folded in, optional LeakyReLU' of the producer), parameter gradients (ACCUMULATED). */
@@ -404,6 +435,8 @@ int vxb_conv3_c1_fwd_f32(const float* u, const float* w, const float* bias, floa
                          vxb_stream_t stream);
 int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
                            int accumulate, int apply_lrelu_mask, float slope, vxb_stream_t stream);
+int vxb_conv3_c1_dgrad_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C, int accumulate,
+                               int apply_lrelu_mask, int act, float slope, vxb_stream_t stream);
 int vxb_conv3_c1_wgrad_f32(const float* u, const float* dq, float* dw, float* db, float* part_ws, int B, int S, int C,
                            vxb_stream_t stream);
 /* Matrix-core versions of the two entries above for the 'bf16x3' / 'bf16' precisions (bf16x3 products, fp32 accumulate):
@@ -432,10 +465,17 @@ size_t vxb_conv3_c1_wgrad_mfma_blocks(int B, int S);
 int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
                                float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
                                int32_t* argmax, vxb_stream_t stream);
+int vxb_pointwise_ss3d_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin,
+                                   int Cout, int act, float slope, const float* lin, float* part_ws, float* out_ss,
+                                   float* out_max, float* stats, int32_t* argmax, vxb_stream_t stream);
 int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
                                  int S, int Cin, int Cout, float slope, const float* lin, const float* stats,
                                  const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
                                  const float* fold_src, int Sp, int pad, vxb_stream_t stream);
+int vxb_pointwise_wgrad_ss3d_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
+                                     int B, int S, int Cin, int Cout, int act, float slope, const float* lin,
+                                     const float* stats, const float* out_ss, const int32_t* argmax, const float* g_ss,
+                                     const float* g_max, const float* fold_src, int Sp, int pad, vxb_stream_t stream);
 
 /* Backward of everything that reads u = final(...) (perceiver_lang_io.py:462-470) in one pass over u: du = lrelu'(u) *
  * ([du if accumulate] + data gradient of trans_decoder (Cout = 1 conv, vxb_conv3_c1_dgrad_f32) + the pooled-feature term of
@@ -446,6 +486,10 @@ int vxb_conv3_c1_dgrad_ss3d_f32(const float* dq, const float* w, const float* u,
                                 int accumulate, float slope, const float* lin, const float* stats, const float* out_ss,
                                 const int32_t* argmax, const float* g_ss, const float* g_max, float* dbias,
                                 float* part_ws, float* du_scale, vxb_stream_t stream);
+int vxb_conv3_c1_dgrad_ss3d_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
+                                    int accumulate, int act, float slope, const float* lin, const float* stats,
+                                    const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
+                                    float* dbias, float* part_ws, float* du_scale, vxb_stream_t stream);
 
 /* SpatialSoftmax3D (T=0.01, meshgrid 'xy' quirk) + AdaptiveMaxPool3d(1) in one streaming pass
  * (network_utils.py:773-809; perceiver_lang_io.py:360,:451,:470), and the backward of both.
@@ -472,6 +516,9 @@ size_t vxb_patch_wgrad_weight_ws_floats(int k, int nsplit);
 int vxb_patch_dgrad_input_wgrad_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V, int G,
                                     int k, int pad, float slope, const float* scale, float* ws, int nsplit, float* dW, float* db,
                                     float* dWp, float* ws_wp, vxb_stream_t stream);
+int vxb_patch_dgrad_input_wgrad_act_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B,
+                                        int V, int G, int k, int pad, int act, float slope, const float* scale, float* ws,
+                                        int nsplit, float* dW, float* db, float* dWp, float* ws_wp, vxb_stream_t stream);
 
 /* PreNorm LayerNorm (perceiver_lang_io.py:56-71), eps 1e-5.  bwd: dgamma/dbeta ACCUMULATED; part_ws: ceil(rows / 32) * 2 * D floats. */
 int vxb_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean,
@@ -565,6 +612,7 @@ int vxb_flash_attn_bwd_dl(const float* q, const float* kv, const float* o, const
 int vxb_geglu_fwd_f32(const float* h, float* out, int64_t rows, int F, vxb_stream_t stream);
 int vxb_geglu_bwd_f32(const float* h, const float* dout, float* dh, int64_t rows, int F, vxb_stream_t stream);
 int vxb_lrelu_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, float slope, vxb_stream_t stream);
+int vxb_lrelu_bwd_act_f32(const float* dy, const float* y, float* dx, int64_t n, int act, float slope, vxb_stream_t stream);
 int vxb_axpy_f32(float* dst, const float* src, int64_t n, float alpha, vxb_stream_t stream);
 
 /* deterministic reductions: dst (+)= alpha * sum_s part[s][:];  out (+)= column sums of x[rows,N]. */

@@ -149,11 +149,14 @@ class PerceiverVoxelLangEncoder(nn.Module):
                  _two_robots=False):
         super().__init__()
         if lang_fusion_type not in ('seq', 'concat') or (lang_fusion_type == 'concat' and (pos_encoding_with_lang or _two_robots)) \
-                or iterations < 1 or activation != 'lrelu' or low_dim_size <= 0 \
+                or iterations < 1 or low_dim_size <= 0 \
                 or num_rotation_classes <= 0:
             raise NotImplementedError(
                 'voxactb_amd covers the configuration VoxAct-B trains (launch_utils.py:744-774, PERACT_BC.yaml): '
-                "lang_fusion_type='seq' (or 'concat' with pos_encoding_with_lang=False, the only combination the reference's forward accepts: perceiver :391 vs :422), activation='lrelu' (+ transformer_iterations >= 1 and the no_language / no_skip_connection / no_perceiver ablations)")
+                "lang_fusion_type='seq' (or 'concat' with pos_encoding_with_lang=False, the only combination the reference's forward accepts: perceiver :391 vs :422), activation 'lrelu', 'relu' or 'tanh' (+ transformer_iterations >= 1 and the no_language / no_skip_connection / no_perceiver ablations)")
+        if activation not in ops.ACTIVATIONS:
+            # the reference's Conv3DBlock raises ValueError() for every other value (network_utils.py:140-154; 'elu' / 'prelu' included)
+            raise ValueError('%s not recognized: the encoder builds with activation %s' % (activation, ' / '.join(sorted(ops.ACTIVATIONS))))
         if im_channels != 64 or final_dim != 64 or int(initial_dim) > 16:
             raise NotImplementedError('kernels are specialised for im_channels = final_dim = 64, initial_dim <= 16')
         if voxel_size % voxel_patch_stride or voxel_patch_size % 2 == 0:
@@ -168,6 +171,7 @@ class PerceiverVoxelLangEncoder(nn.Module):
         self.input_dropout, self.attn_dropout, self.decoder_dropout = input_dropout, attn_dropout, decoder_dropout
         self.no_skip_connection, self.no_perceiver, self.no_language = no_skip_connection, no_perceiver, no_language
         self.arm_pred_loss = arm_pred_loss
+        self.activation = activation
         self.two_robots = bool(_two_robots)       # one_policy_more_heads baseline (reference class PerceiverVoxelLang2RobotsEncoder)
         self.cross_heads, self.latent_heads = cross_heads, latent_heads
         self.cross_dim_head, self.latent_dim_head = cross_dim_head, latent_dim_head
@@ -312,6 +316,9 @@ class PerceiverEngine:
         self.C = module.im_channels
         self.Cx = module.input_dim_before_seq
         self.two = bool(getattr(module, 'two_robots', False))
+        # (code, slope) of the encoder's activation, passed to every op that applies it or its derivative (no process-wide state:
+        # engines of different activations run interleaved)
+        self.act = ops.ACTIVATIONS[getattr(module, 'activation', 'lrelu')]
         self.D = module.latent_dim
         self.L = module.num_latents
         self.concat = getattr(module, 'lang_fusion_type', 'seq') == 'concat'
@@ -649,15 +656,15 @@ class PerceiverEngine:
         # 2. SpatialSoftmax3D + max (perceiver :360) -- taken while d0 is written (one pass over the 256 B per voxel)
         if C == 64 and FUSE_INPUT_SS:
             d0, ss0 = ops.pointwise_ss3d_fwd(vox, self.p('input_preprocess.conv3d.weight').view(C, -1),
-                                             self.p('input_preprocess.conv3d.bias'), B, V)
+                                             self.p('input_preprocess.conv3d.bias'), B, V, act=self.act)
         else:
-            d0 = ops.pointwise_fwd(vox, self.p('input_preprocess.conv3d.weight').view(C, -1), self.p('input_preprocess.conv3d.bias'))
+            d0 = ops.pointwise_fwd(vox, self.p('input_preprocess.conv3d.weight').view(C, -1), self.p('input_preprocess.conv3d.bias'), act=self.act)
             ss0 = ops.ss3d_max_fwd(d0, V ** 3 * C, B, V, C)
         # 3. patchify (perceiver :363)
         patch = ops.conv3d(d0, ops.conv_weight_fwd(self.p('patchify.conv3d.weight')), C, B, V, G, k, -(k // 2), stride=s,
-                           bias=self.p('patchify.conv3d.bias'), act=ops.ACT_LRELU)
+                           bias=self.p('patchify.conv3d.bias'), act=self.act)
         # 4-6. proprio, language, context assembly (perceiver :370-422)
-        pp = ops.linear(proprio, self.p('proprio_preprocess.linear.weight'), self.p('proprio_preprocess.linear.bias'), ops.ACT_LRELU)
+        pp = ops.linear(proprio, self.p('proprio_preprocess.linear.weight'), self.p('proprio_preprocess.linear.bias'), self.act)
         lg = ops.linear(lang, self.p('lang_preprocess.weight'), self.p('lang_preprocess.bias'))
         ppc = torch.cat((pp[:B], pp[B:]), dim=1) if self.two else pp          # [B, C] or [B, right C | left C]
         if self.concat:                                                       # [B, proprio C | language C]: channels of every grid token
@@ -706,7 +713,7 @@ class PerceiverEngine:
         zc = zv.contiguous().view(B, G, G, G, Cx)
         # up0 = conv(k) -> upsample(s) -> conv(k)   (perceiver :454; network_utils :242-250)
         z1 = ops.conv3d(zc, ops.conv_weight_fwd(self.p('up0.conv_up.0.conv3d.weight')), C, B, G, G, k, -(k // 2),
-                        bias=self.p('up0.conv_up.0.conv3d.bias'), act=ops.ACT_LRELU)
+                        bias=self.p('up0.conv_up.0.conv3d.bias'), act=self.act)
         up2 = 'up0.conv_up.%d.conv3d' % (2 if s > 1 else 1)
         if s > 1:
             if self._frozen_now and self._weff_keep is not None:
@@ -715,34 +722,34 @@ class PerceiverEngine:
                 Weff = ops.polyphase_weights(self.p(up2 + '.weight'), self.Lt(dev), s, self.kl)
                 self._weff_keep = Weff if self._frozen_now else None
             if ops.polyphase_fwd_ok(C, C, self.kl, B, G):
-                u0 = ops.conv3_polyphase_fwd(z1, Weff, C, B, G, k, s, self.p(up2 + '.bias').repeat(s ** 3), act=ops.ACT_LRELU)
+                u0 = ops.conv3_polyphase_fwd(z1, Weff, C, B, G, k, s, self.p(up2 + '.bias').repeat(s ** 3), act=self.act)
             else:
                 u0 = ops.conv3d(z1, Weff, s ** 3 * C, B, G, G, self.kl, -self.R, bias=self.p(up2 + '.bias').repeat(s ** 3),
-                                act=ops.ACT_LRELU, d2s=(s, C))
+                                act=self.act, d2s=(s, C))
         else:
             Weff = None
             u0 = ops.conv3d(z1, ops.conv_weight_fwd(self.p(up2 + '.weight')), C, B, G, G, k, -(k // 2),
-                            bias=self.p(up2 + '.bias'), act=ops.ACT_LRELU)
+                            bias=self.p(up2 + '.bias'), act=self.act)
         # ablations (perceiver :457-460): `final` reads u0 alone (no_skip_connection) or d0 alone (no_perceiver: the transformer still runs,
         # its latents reach the heads through ss1) -- one 64-channel source on the generic kernels
         skip = 'u0' if m.no_skip_connection else ('d0' if m.no_perceiver else 'cat')
         if skip != 'cat':
             u = ops.conv3d(u0 if skip == 'u0' else d0, ops.conv_weight_fwd(self.p('final.conv3d.weight')), C, B, V, V, 3, -1,
-                           bias=self.p('final.conv3d.bias'), act=ops.ACT_LRELU)
+                           bias=self.p('final.conv3d.bias'), act=self.act)
             ss2 = ops.ss3d_max_fwd(u, V ** 3 * C, B, V, C)
         # final conv over cat([d0, u0]) without the cat (perceiver :462)
         elif ops.conv3_ss3d_ok(C, C, C, V):
             # ... with the pooled features of its output (:470) taken in the conv's epilogue: no statistics pass over u
-            u, ss2 = ops.conv3_ss3d_fwd(d0, u0, ops.conv_weight_fwd(self.p('final.conv3d.weight')), self.p('final.conv3d.bias'), B, V)
+            u, ss2 = ops.conv3_ss3d_fwd(d0, u0, ops.conv_weight_fwd(self.p('final.conv3d.weight')), self.p('final.conv3d.bias'), B, V, act=self.act)
         else:
             u = ops.conv3d(d0, ops.conv_weight_fwd(self.p('final.conv3d.weight')), C, B, V, V, 3, -1,
-                           bias=self.p('final.conv3d.bias'), act=ops.ACT_LRELU, src1=u0)
+                           bias=self.p('final.conv3d.bias'), act=self.act, src1=u0)
             ss2 = ops.ss3d_max_fwd(u, V ** 3 * C, B, V, C)
         # translation head (perceiver :465)
         q_trans = ops.conv3_c1_fwd(u, self.p('trans_decoder.conv3d.weight'), self.p('trans_decoder.conv3d.bias'), B, V)
         feats = torch.cat([ss0[0], ss0[1], ss1[0], ss1[1], ss2[0], ss2[1]], dim=1)
-        h0 = ops.linear(feats, self.p('dense0.linear.weight'), self.p('dense0.linear.bias'), ops.ACT_LRELU)
-        h1 = ops.linear(h0, self.p('dense1.linear.weight'), self.p('dense1.linear.bias'), ops.ACT_LRELU)
+        h0 = ops.linear(feats, self.p('dense0.linear.weight'), self.p('dense0.linear.bias'), self.act)
+        h1 = ops.linear(h0, self.p('dense1.linear.weight'), self.p('dense1.linear.bias'), self.act)
         o = ops.linear(h1, self.p('rot_grip_collision_ff.linear.weight'), self.p('rot_grip_collision_ff.linear.bias'))
         nc = m.num_collision_classes
         outs = (q_trans.view(B, 1, V, V, V), o[:, :-nc], o[:, -nc:])
@@ -751,14 +758,14 @@ class PerceiverEngine:
             # left arm: its own translation conv and MLP head over the SAME pooled features (ss_final_left_arm(u) is
             # ss_final(u): SpatialSoftmax3D has no parameters; perceiver :845-858)
             q_left = ops.conv3_c1_fwd(u, self.p('trans_decoder_left_arm.conv3d.weight'), self.p('trans_decoder_left_arm.conv3d.bias'), B, V)
-            h0l = ops.linear(feats, self.p('dense0_left_arm.linear.weight'), self.p('dense0_left_arm.linear.bias'), ops.ACT_LRELU)
-            h1l = ops.linear(h0l, self.p('dense1_left_arm.linear.weight'), self.p('dense1_left_arm.linear.bias'), ops.ACT_LRELU)
+            h0l = ops.linear(feats, self.p('dense0_left_arm.linear.weight'), self.p('dense0_left_arm.linear.bias'), self.act)
+            h1l = ops.linear(h0l, self.p('dense1_left_arm.linear.weight'), self.p('dense1_left_arm.linear.bias'), self.act)
             ol = ops.linear(h1l, self.p('rot_grip_collision_ff_left_arm.linear.weight'), self.p('rot_grip_collision_ff_left_arm.linear.bias'))
             outs = outs + (q_left.view(B, 1, V, V, V), ol[:, :-nc], ol[:, -nc:])
             left = dict(h0=h0l, h1=h1l, o=ol)
         h2 = None
         if m.arm_pred_loss:
-            h2 = ops.linear(feats, self.p('dense2.linear.weight'), self.p('dense2.linear.bias'), ops.ACT_LRELU)
+            h2 = ops.linear(feats, self.p('dense2.linear.weight'), self.p('dense2.linear.bias'), self.act)
             outs = outs + (ops.linear(h2, self.p('arm_ff.linear.weight'), self.p('arm_ff.linear.bias')),)
         if save:
             c.update(B=B, vox=vox, proprio=proprio, lang=lang, d0=d0, ss0=ss0, patch=patch, pp=pp, ctx2d=ctx2d,
@@ -811,17 +818,17 @@ class PerceiverEngine:
         dh1 = E(B, c['h1'].shape[1])
         ops.linear_bwd(c['h1'], self.p('rot_grip_collision_ff.linear.weight'), d_o.contiguous(),
                        self.g('rot_grip_collision_ff.linear.weight'), self.g('rot_grip_collision_ff.linear.bias'), dh1)
-        ops.lrelu_bwd_(dh1, c['h1'])
+        ops.lrelu_bwd_(dh1, c['h1'], act=self.act)
         dh0 = E(B, 256)
         ops.linear_bwd(c['h0'], self.p('dense1.linear.weight'), dh1, self.g('dense1.linear.weight'), self.g('dense1.linear.bias'), dh0)
-        ops.lrelu_bwd_(dh0, c['h0'])
+        ops.lrelu_bwd_(dh0, c['h0'], act=self.act)
         dfe = E(B, c['feats'].shape[1])
         ops.linear_bwd(c['feats'], self.p('dense0.linear.weight'), dh0, self.g('dense0.linear.weight'), self.g('dense0.linear.bias'), dfe)
         if m.arm_pred_loss and d_arm is not None:
             dh2 = E(B, C)
             ops.linear_bwd(c['h2'], self.p('arm_ff.linear.weight'), d_arm.contiguous(), self.g('arm_ff.linear.weight'),
                            self.g('arm_ff.linear.bias'), dh2)
-            ops.lrelu_bwd_(dh2, c['h2'])
+            ops.lrelu_bwd_(dh2, c['h2'], act=self.act)
             ops.linear_bwd(c['feats'], self.p('dense2.linear.weight'), dh2, self.g('dense2.linear.weight'),
                            self.g('dense2.linear.bias'), dfe, dx_accumulate=True)
         if self.two:
@@ -831,11 +838,11 @@ class PerceiverEngine:
             dh1l = E(B, cl['h1'].shape[1])
             ops.linear_bwd(cl['h1'], self.p('rot_grip_collision_ff_left_arm.linear.weight'), d_o_left.contiguous(),
                            self.g('rot_grip_collision_ff_left_arm.linear.weight'), self.g('rot_grip_collision_ff_left_arm.linear.bias'), dh1l)
-            ops.lrelu_bwd_(dh1l, cl['h1'])
+            ops.lrelu_bwd_(dh1l, cl['h1'], act=self.act)
             dh0l = E(B, 256)
             ops.linear_bwd(cl['h0'], self.p('dense1_left_arm.linear.weight'), dh1l, self.g('dense1_left_arm.linear.weight'),
                            self.g('dense1_left_arm.linear.bias'), dh0l)
-            ops.lrelu_bwd_(dh0l, cl['h0'])
+            ops.lrelu_bwd_(dh0l, cl['h0'], act=self.act)
             ops.linear_bwd(c['feats'], self.p('dense0_left_arm.linear.weight'), dh0l, self.g('dense0_left_arm.linear.weight'),
                            self.g('dense0_left_arm.linear.bias'), dfe, dx_accumulate=True)
         o0 = 0
@@ -857,16 +864,16 @@ class PerceiverEngine:
         if self.two:
             dql = dq_trans_left.contiguous().view(B, V, V, V)
             ops.conv3_c1_wgrad(u, dql, self.g('trans_decoder_left_arm.conv3d.weight'), self.g('trans_decoder_left_arm.conv3d.bias'), B, V)
-            ops.conv3_c1_dgrad(dql, self.p('trans_decoder_left_arm.conv3d.weight'), u, du, B, V, accumulate=not fuse_u, mask=False)
+            ops.conv3_c1_dgrad(dql, self.p('trans_decoder_left_arm.conv3d.weight'), u, du, B, V, accumulate=not fuse_u, mask=False, act=self.act)
         f16_leaf = ops.WGRAD_PRECISION == 'fp16' and C == 64 and ops.dgrad_fold_ok(C, 2 * C, V)
         sc_du = None
         if fuse_u:
             r = ops.conv3_c1_dgrad_ss3d(dq_trans, wt, u, du, B, V, st, ss, am, gs[4], gs[5], self.g('final.conv3d.bias'),
-                                        accumulate=self.two, want_scale=f16_leaf)
+                                        accumulate=self.two, want_scale=f16_leaf, act=self.act)
             if f16_leaf:
                 sc_du = r[1]
         else:
-            ops.conv3_c1_dgrad(dq_trans, wt, u, du, B, V, accumulate=True, mask=True)      # du is now d(pre-activation of `final`)
+            ops.conv3_c1_dgrad(dq_trans, wt, u, du, B, V, accumulate=True, mask=True, act=self.act)      # du is now d(pre-activation of `final`)
         # ---- final conv (two sources)
         Wf = self.p('final.conv3d.weight')
         # one |du| maximum serves both single-fp16-product kernels that read du (the weight gradient and the d(d0) half of the data
@@ -904,9 +911,9 @@ class PerceiverEngine:
         if skip != 'cat':
             dsrc = ops.conv3d(du, ops.conv_weight_dgrad(Wf), C, B, V, V + 2, 3, -2, replicate=False)
             if skip == 'u0':
-                ops.fold_pad(dsrc, V + 2, C, 0, du0, B, V, C, 1, lrelu_of=u0)         # d(pre-activation of up0's last conv)
+                ops.fold_pad(dsrc, V + 2, C, 0, du0, B, V, C, 1, lrelu_of=u0, act=self.act)         # d(pre-activation of up0's last conv)
             else:
-                ops.fold_pad(dsrc, V + 2, C, 0, dd0, B, V, C, 1, accumulate=not fuse_ss0)
+                ops.fold_pad(dsrc, V + 2, C, 0, dd0, B, V, C, 1, accumulate=not fuse_ss0, act=self.act)
             del dsrc
         elif C == 64 and ops.dgrad_fold_ok(C, 2 * C, V):
             # data gradient and the adjoint of the replicate padding in one kernel: the first 64 columns go (add) into dd0,
@@ -916,12 +923,12 @@ class PerceiverEngine:
             up2b = 'up0.conv_up.%d.conv3d.bias' % (2 if s > 1 else 1)
             sc_du0 = ops.conv3_dgrad_fold(du, ops.conv_weight_dgrad(Wf), B, V, 2 * C, [(dd0, not fuse_ss0, None), (du0, False, u0)],
                                           dy_scale=sc_du, leaf_blocks=(0,), scale_blocks=(1,), colsum_into={1: self.g(up2b)},
-                                          wgin={0: (d0, c['vox'], gW_in, gb_in)} if no_dd0 else None).get(1)
+                                          wgin={0: (d0, c['vox'], gW_in, gb_in)} if no_dd0 else None, act=self.act).get(1)
             du0_bias_done = True
         else:
             dcat = ops.conv3d(du, ops.conv_weight_dgrad(Wf), 2 * C, B, V, V + 2, 3, -2, replicate=False)
-            ops.fold_pad(dcat, V + 2, 2 * C, 0, dd0, B, V, C, 1, accumulate=not fuse_ss0)
-            ops.fold_pad(dcat, V + 2, 2 * C, C, du0, B, V, C, 1, lrelu_of=u0)         # d(pre-activation of up0's last conv)
+            ops.fold_pad(dcat, V + 2, 2 * C, 0, dd0, B, V, C, 1, accumulate=not fuse_ss0, act=self.act)
+            ops.fold_pad(dcat, V + 2, 2 * C, C, du0, B, V, C, 1, lrelu_of=u0, act=self.act)         # d(pre-activation of up0's last conv)
             del dcat
         del du
         dzp = None
@@ -948,12 +955,12 @@ class PerceiverEngine:
                 else:
                     wd = ops.polyphase_dgrad_weights(c['Weff'], C, C, s, kl)
                     dzp = ops.conv3d(du0, wd, C, B, V, Sp, s * kl, -s * (kl - 1), stride=s, replicate=False)
-                ops.fold_pad(dzp, Sp, C, 0, dz1, B, G, C, R, lrelu_of=z1)
+                ops.fold_pad(dzp, Sp, C, 0, dz1, B, G, C, R, lrelu_of=z1, act=self.act)
             else:
                 dWt = ops.conv3d_wgrad(z1, du0, C, B, G, G, k, -(k // 2))
                 self.g(up2 + '.weight').add_(dWt.view(k ** 3, C, C).permute(2, 1, 0).reshape(W2.shape))
                 dzp = ops.conv3d(du0, ops.conv_weight_dgrad(W2), C, B, G, G + 2 * (k // 2), k, -(k - 1), replicate=False)
-                ops.fold_pad(dzp, G + 2 * (k // 2), C, 0, dz1, B, G, C, k // 2, lrelu_of=z1)
+                ops.fold_pad(dzp, G + 2 * (k // 2), C, 0, dz1, B, G, C, k // 2, lrelu_of=z1, act=self.act)
             del du0, dzp
             W1 = self.p('up0.conv_up.0.conv3d.weight')
             dWt = ops.conv3d_wgrad(zc, dz1, C, B, G, G, k, -(k // 2), grad_key=('conv', W1.data_ptr()))
@@ -965,7 +972,7 @@ class PerceiverEngine:
         ss, mx, st, am = c['ss1']
         ops.ss3d_max_bwd(c['z'][:, T0:], Nctx * Cx, B, G, Cx, st, ss, am, gs[2], gs[3], dzv, T1 * Cx)
         if dzp is not None:
-            ops.fold_pad(dzp, G + 2 * pk, Cx, 0, dzv, B, G, Cx, pk, accumulate=True)
+            ops.fold_pad(dzp, G + 2 * pk, Cx, 0, dzv, B, G, Cx, pk, accumulate=True, act=self.act)
         dz = torch.zeros((B, Nctx, Cx), dtype=torch.float32, device=dev)
         dz[:, T0:] = dzv
         # ---- decoder cross attention
@@ -1018,11 +1025,11 @@ class PerceiverEngine:
             dlang, dpp = dpp[:, C:].contiguous(), dpp[:, :C].contiguous()
         ops.linear_bwd(c['lang'], self.p('lang_preprocess.weight'), dlang, self.g('lang_preprocess.weight'),
                        self.g('lang_preprocess.bias'))
-        ops.lrelu_bwd_(dpp, c['pp'])
+        ops.lrelu_bwd_(dpp, c['pp'], act=self.act)
         ops.linear_bwd(c['proprio'], self.p('proprio_preprocess.linear.weight'), dpp, self.g('proprio_preprocess.linear.weight'),
                        self.g('proprio_preprocess.linear.bias'))
         # ---- patchify
-        ops.lrelu_bwd_(dpatch, c['patch'])
+        ops.lrelu_bwd_(dpatch, c['patch'], act=self.act)
         fuse_patch = fuse_ss0 and ops.patch_dgrad_input_wgrad_ok(k, s, C, c['vox'].shape[-1]) and (dpatch.is_contiguous() or no_dd0)
         # (fused path: the patchify weight gradient comes out of the launch that already reads d0 for the input conv's gradient)
         wp_in_fused = fuse_patch and ops.PATCH_WGRAD_WEIGHT and self.g('patchify.conv3d.weight').is_contiguous()
@@ -1036,7 +1043,7 @@ class PerceiverEngine:
             # the patchify data gradient only feeds the input conv's weight gradient (the voxel grid is a detached input): its share
             # of dW_in / db_in straight from dpatch, no 105^3 x 64 gradient tensor (patch_wgrad.hip)
             ops.patch_dgrad_input_wgrad(dpatch, Wp, d0, c['vox'], gW_in, gb_in, B, V, G, k, pk,
-                                        dWp=self.g('patchify.conv3d.weight') if wp_in_fused else None)
+                                        dWp=self.g('patchify.conv3d.weight') if wp_in_fused else None, act=self.act)
         elif s > 1:
             wtp, U = ops.strided_dgrad_weights(Wp, s)
             Gp = (V + 2 * pk + s - 1) // s
@@ -1046,13 +1053,13 @@ class PerceiverEngine:
             dxp = ops.conv3d(dpatch, ops.conv_weight_dgrad(Wp), C, B, G, V + 2 * pk, k, -(k - 1), replicate=False)
             Sp = V + 2 * pk
         if not fuse_ss0:          # (fused: the padding adjoint of dxp is gathered inside the input conv's weight-gradient kernel)
-            ops.fold_pad(dxp, Sp, C, 0, dd0, B, V, C, pk, accumulate=True)
+            ops.fold_pad(dxp, Sp, C, 0, dd0, B, V, C, pk, accumulate=True, act=self.act)
         # ---- input conv (its LeakyReLU' is applied inside the weight-gradient kernel)
         if fuse_ss0:
             ss, mx, st, am = c['ss0']
-            ops.pointwise_wgrad_ss3d(c['vox'], d0, dd0, gW_in, gb_in, B, V, st, ss, am, gs[0], gs[1], fold_src=dxp, Sp=Sp, pad=pk)
+            ops.pointwise_wgrad_ss3d(c['vox'], d0, dd0, gW_in, gb_in, B, V, st, ss, am, gs[0], gs[1], fold_src=dxp, Sp=Sp, pad=pk, act=self.act)
         else:
-            ops.pointwise_wgrad(c['vox'], d0, dd0, gW_in, gb_in)
+            ops.pointwise_wgrad(c['vox'], d0, dd0, gW_in, gb_in, act=self.act)
         self._bucket_ready('head')
 
     def _bucket_ready(self, name):

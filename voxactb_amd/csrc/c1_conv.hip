@@ -17,7 +17,7 @@ __device__ __forceinline__ void c1_fma4(float4& a, float g, const float4 w) {
 // groups touching a face take the table-driven path with the weights in LDS.
 __global__ void __launch_bounds__(256, 4) c1_dgrad4_kernel(const float* __restrict__ dq, const float* __restrict__ w,
                                                         const float* __restrict__ u, float* __restrict__ du, int B, int S,
-                                                        int accumulate, int mask, float slope) {
+                                                        int accumulate, int mask, int act, float slope) {
     __shared__ float sw[27 * 64];          // [t][c]
     for (int i = threadIdx.x; i < 27 * 64; i += 256) sw[(i % 27) * 64 + i / 27] = w[i];
     const int c4 = (threadIdx.x & 15) * 4, gl = threadIdx.x >> 4;
@@ -89,8 +89,8 @@ __global__ void __launch_bounds__(256, 4) c1_dgrad4_kernel(const float* __restri
             }
             if (mask) {
                 const float4 uu = *reinterpret_cast<const float4*>(u + o);
-                r.x = uu.x > 0.f ? r.x : r.x * slope; r.y = uu.y > 0.f ? r.y : r.y * slope;
-                r.z = uu.z > 0.f ? r.z : r.z * slope; r.w = uu.w > 0.f ? r.w : r.w * slope;
+                r.x = act_bwd(r.x, uu.x, act, slope); r.y = act_bwd(r.y, uu.y, act, slope);
+                r.z = act_bwd(r.z, uu.z, act, slope); r.w = act_bwd(r.w, uu.w, act, slope);
             }
             *reinterpret_cast<float4*>(du + o) = r;
         }
@@ -103,9 +103,10 @@ __global__ void __launch_bounds__(256, 4) c1_dgrad4_kernel(const float* __restri
 // of the finished du (= the bias gradient of the conv that produced u) are taken while du is in registers instead of by a
 // colsum pass.  du = lrelu'(u) * ([du_in] + sum_t dq w + ss term); partB[block][64] = sum over the block's voxels of du.
 // One sample per blockIdx.y, so the per-(sample, channel) softmax constants stay in registers.
+template <bool TANH>
 __global__ void __launch_bounds__(256, 2) c1_dgrad4_ss_kernel(const float* __restrict__ dq, const float* __restrict__ w,
                                                            const float* __restrict__ u, float* __restrict__ du, int S,
-                                                           int accumulate, float slope, const float* __restrict__ lin,
+                                                           int accumulate, int act, float slope, const float* __restrict__ lin,
                                                            const float* __restrict__ stats, const float* __restrict__ out_ss,
                                                            const int* __restrict__ argmax, const float* __restrict__ g_ss,
                                                            const float* __restrict__ g_max, float* __restrict__ partB,
@@ -239,7 +240,7 @@ __global__ void __launch_bounds__(256, 2) c1_dgrad4_ss_kernel(const float* __res
                 if (p == am[e]) g += gm[e];
                 if (accumulate) g = od4[e] + g;
                 float v = ac[e] + g;                        // (same two addends as c1_dgrad4 after ss_bwd4: bit-identical)
-                v = xs[e] > 0.f ? v : v * slope;
+                v = act_bwd_t<TANH>(v, xs[e], slope);
                 bsum[e] += v;
                 r[e] = v;
                 amxf = fmaxf(amxf, fabsf(v));
@@ -431,10 +432,10 @@ int vxb_c1_fwd4_launch(const float* u, const float* w, const float* bias, float*
 
 // launchers used by the C entry points in vox_ops.hip when S % 4 == 0
 int vxb_c1_dgrad4_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, int mask,
-                         float slope, hipStream_t st) {
+                         int act, float slope, hipStream_t st) {
     const long long ngroups = (long long)B * S * S * (S >> 2);
     const int grid = (int)((ngroups + 15) / 16 > 16384 ? 16384 : (ngroups + 15) / 16);
-    hipLaunchKernelGGL(c1_dgrad4_kernel, dim3(grid), dim3(256), 0, st, dq, w, u, du, B, S, accumulate, mask, slope);
+    hipLaunchKernelGGL(c1_dgrad4_kernel, dim3(grid), dim3(256), 0, st, dq, w, u, du, B, S, accumulate, mask, act, slope);
     return hipGetLastError() == hipSuccess ? VXB_OK : VXB_ELAUNCH;
 }
 
@@ -443,11 +444,13 @@ int vxb_c1_dgrad_ss_blocks_per_sample(int S) {
     const long long g = (long long)S * S * (S >> 2);
     return (int)((g + 15) / 16 > 1024 ? 1024 : (g + 15) / 16);
 }
-int vxb_c1_dgrad4_ss_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, float slope,
+int vxb_c1_dgrad4_ss_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, int act, float slope,
                             const float* lin, const float* stats, const float* out_ss, const int* argmax, const float* g_ss,
                             const float* g_max, float* dbias, float* part_ws, unsigned* part_amax, hipStream_t st) {
     const int nbx = vxb_c1_dgrad_ss_blocks_per_sample(S);
-    hipLaunchKernelGGL(c1_dgrad4_ss_kernel, dim3(nbx, B), dim3(256), 0, st, dq, w, u, du, S, accumulate, slope, lin, stats, out_ss,
+    slope = vxb_lrelu_slope(act, slope);
+    auto kern = act == VXB_ACT_TANH ? c1_dgrad4_ss_kernel<true> : c1_dgrad4_ss_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(nbx, B), dim3(256), 0, st, dq, w, u, du, S, accumulate, act, slope, lin, stats, out_ss,
                        argmax, g_ss, g_max, part_ws, part_amax);
     // two stages (fixed order): 64 workgroups fold nb / 64 partial rows each into the head of a second buffer, one more folds those
     const int nb = nbx * B, per = (nb + 63) / 64;

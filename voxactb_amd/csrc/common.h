@@ -21,7 +21,7 @@ static inline int vxb_cdiv(long long a, long long b) { return (int)((a + b - 1) 
 // float4 variants of the Cout = 1 conv kernels (c1_conv.hip), used by the C entry points in vox_ops.hip when S % 4 == 0
 int vxb_c1_fwd4_launch(const float* u, const float* w, const float* bias, float* q, int B, int S, hipStream_t st);
 int vxb_c1_dgrad_ss_blocks_per_sample(int S);
-int vxb_c1_dgrad4_ss_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, float slope,
+int vxb_c1_dgrad4_ss_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, int act, float slope,
                             const float* lin, const float* stats, const float* out_ss, const int* argmax, const float* g_ss,
                             const float* g_max, float* dbias, float* part_ws, unsigned* part_amax, hipStream_t st);
 // scale[0] = 2^k mapping the largest of n per-block |x| maxima (magnitude bits) into [2^14, 2^15), scale[1] = 1 / scale[0] (nn_ops.hip)
@@ -38,10 +38,45 @@ int vxb_rows64_sum_launch(float* part, int nrows, float* out, hipStream_t st);
 int vxb_ss3d_final_tiles_launch(const float* part, int ntiles, int B, int C, float* out_ss, float* out_max, float* stats, int32_t* argmax,
                                 hipStream_t st);
 int vxb_c1_dgrad4_launch(const float* dq, const float* w, const float* u, float* du, int B, int S, int accumulate, int mask,
-                         float slope, hipStream_t st);
+                         int act, float slope, hipStream_t st);
 int vxb_c1_wgrad4_launch(const float* u, const float* dq, float* dw, float* db, float* part_ws, int B, int S, hipStream_t st);
 
 constexpr int WAVE = 64;
+
+// Activation of the conv / linear epilogues (include/voxactb_hip.h, "Activation codes"): 0 none, 1 LeakyReLU(slope) (ReLU = slope 0),
+// 2 tanh.  The backward forms take the SAVED OUTPUT y: LeakyReLU' gates on y > 0 (as PyTorch's ReLU / LeakyReLU backward do), tanh' is
+// 1 - y^2 (PyTorch's tanh_backward).  act == 1 is the expression the kernels inlined before, so the LeakyReLU path keeps its bits.
+constexpr int VXB_ACT_NONE = 0, VXB_ACT_LRELU = 1, VXB_ACT_TANH = 2;
+static inline bool vxb_act_ok(int act) { return act >= VXB_ACT_NONE && act <= VXB_ACT_TANH; }
+// the slope a kernel with the LeakyReLU select built in (act_bwd_t<false>, lrelu_or_tanh<false>) applies for code `act`: code 0 (no
+// activation) is LeakyReLU with slope 1 there -- x * 1 is x
+static inline float vxb_lrelu_slope(int act, float slope) { return act == VXB_ACT_NONE ? 1.f : slope; }
+__device__ __forceinline__ float act_fwd(float x, int act, float slope) {
+    if (act == VXB_ACT_LRELU) return x > 0.f ? x : x * slope;
+    if (act == VXB_ACT_TANH) return tanhf(x);          // ocml tanhf (tests/test_activation_gpu.py: within 3e-7 of float64 tanh)
+    return x;
+}
+// (no control flow: d * 1 and d * slope are the bits of the LeakyReLU select)
+__device__ __forceinline__ float act_bwd(float d, float y, int act, float slope) {
+    const float f = act == VXB_ACT_TANH ? 1.f - y * y : (y > 0.f || act == VXB_ACT_NONE) ? 1.f : slope;
+    return d * f;
+}
+// The same with tanh decided at compile time, for kernels whose LeakyReLU build keeps the code (and register allocation) it had before
+// the tanh code existed: the launcher instantiates TANH = (act == 2); TANH = false is act 0 / 1 as at run time above (backward: act 1 --
+// the entries pass act 0 as LeakyReLU with slope 1).
+template <bool TANH> __device__ __forceinline__ float act_fwd_t(float x, int act, float slope) {
+    if constexpr (TANH) return tanhf(x);
+    else return act == VXB_ACT_LRELU ? (x > 0.f ? x : x * slope) : x;
+}
+// kernels that applied LeakyReLU unconditionally: code 0 / 1 as LeakyReLU with vxb_lrelu_slope(act, slope), tanh by instantiation
+template <bool TANH> __device__ __forceinline__ float lrelu_or_tanh(float x, float slope) {
+    if constexpr (TANH) return tanhf(x);
+    else return x > 0.f ? x : x * slope;
+}
+template <bool TANH> __device__ __forceinline__ float act_bwd_t(float d, float y, float slope) {
+    if constexpr (TANH) return d * (1.f - y * y);
+    else return y > 0.f ? d : d * slope;
+}
 
 // two fp32 -> packed bf16 pair (low half = first value), round-to-nearest-even: one v_cvt_pk_bf16_f32 on gfx950
 typedef __bf16 vxb_bf16x2 __attribute__((ext_vector_type(2)));

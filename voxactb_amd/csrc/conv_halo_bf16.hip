@@ -137,7 +137,7 @@ __device__ __forceinline__ void halo_tile_coords(const HaloArgs& g, int t, int& 
     vxb_tile_block_coords(t, g.ntd, g.nth, g.ntw, td, th, tw);
 }
 
-template <int NTG, int PM, int NW, int WD, int TL, int WN, int HALF, int WG = 0, int BLN = 0>
+template <int NTG, int PM, int NW, int WD, int TL, int WN, int HALF, int WG = 0, int BLN = 0, bool TANH = false>
                                               // NTG = N / 32 column tiles per workgroup; the NW waves form a (NW / WN) x WN grid over
                                               // (8 M tiles) x (NTG column tiles): 4 x 1 -> 2 M tiles x 2 column tiles per wave,
                                               // 2 x 2 -> 4 x 1 (half the B-fragment traffic per MFMA, twice the A reads from LDS),
@@ -925,8 +925,12 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
                     const int jd = min(max(id - P, 0), S - 1), jh = min(max(ih - P, 0), S - 1), jw = min(max(iw - P, 0), S - 1);
                     const long long vox = (((long long)b * S + jd) * S + jh) * S + jw;
                     const float4 yy = *reinterpret_cast<const float4*>(yv + vox * 64 + c4);
-                    a.x = yy.x > 0.f ? a.x : a.x * g.slope; a.y = yy.y > 0.f ? a.y : a.y * g.slope;
-                    a.z = yy.z > 0.f ? a.z : a.z * g.slope; a.w = yy.w > 0.f ? a.w : a.w * g.slope;
+                    if constexpr (TANH) {              // (tanh': its own instantiation; the LeakyReLU select below is the code of ABI 4)
+                        a.x *= 1.f - yy.x * yy.x; a.y *= 1.f - yy.y * yy.y; a.z *= 1.f - yy.z * yy.z; a.w *= 1.f - yy.w * yy.w;
+                    } else {
+                        a.x = yy.x > 0.f ? a.x : a.x * g.slope; a.y = yy.y > 0.f ? a.y : a.y * g.slope;
+                        a.z = yy.z > 0.f ? a.z : a.z * g.slope; a.w = yy.w > 0.f ? a.w : a.w * g.slope;
+                    }
                     const float* xv = wgin_x + vox * 10;
                     float xr[10];
 #pragma unroll
@@ -1002,8 +1006,12 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
             }
             if (yv) {
                 const float4 yy = *reinterpret_cast<const float4*>(yv + o);
-                a.x = yy.x > 0.f ? a.x : a.x * g.slope; a.y = yy.y > 0.f ? a.y : a.y * g.slope;
-                a.z = yy.z > 0.f ? a.z : a.z * g.slope; a.w = yy.w > 0.f ? a.w : a.w * g.slope;
+                if constexpr (TANH) {                  // (tanh': its own instantiation; the LeakyReLU select below is the code of ABI 4)
+                    a.x *= 1.f - yy.x * yy.x; a.y *= 1.f - yy.y * yy.y; a.z *= 1.f - yy.z * yy.z; a.w *= 1.f - yy.w * yy.w;
+                } else {
+                    a.x = yy.x > 0.f ? a.x : a.x * g.slope; a.y = yy.y > 0.f ? a.y : a.y * g.slope;
+                    a.z = yy.z > 0.f ? a.z : a.z * g.slope; a.w = yy.w > 0.f ? a.w : a.w * g.slope;
+                }
             }
             *reinterpret_cast<float4*>(dst + o) = a;
             amxf = fmaxf(fmaxf(amxf, fabsf(a.x)), fmaxf(fmaxf(fabsf(a.y), fabsf(a.z)), fabsf(a.w)));
@@ -1071,7 +1079,7 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
                 for (int j = 0; j < NT; ++j) {
                     const int n = n0 + (wn * NT + j) * 32 + lq;
                     float v = (PM >= 2 ? acc[i][j][r4 + u] * out_sc : acc[i][j][r4 + u]) + (g.bias ? g.bias[n] : 0.f);
-                    if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                    v = act_fwd_t<TANH>(v, g.act, g.slope);
                     if (!(g.dbg & 0x40)) op[n] = v;                  // (0x40: no output stores)
                     vj[j] = v;
                 }
@@ -1132,7 +1140,7 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
     }
 }
 
-template <int NTG, int PM, int NW, int WD, int TL = 0, int WN = 1, int WG = 0, int BLN = 0>
+template <int NTG, int PM, int NW, int WD, int TL = 0, int WN = 1, int WG = 0, int BLN = 0, bool TANH = false>
 __global__ void __launch_bounds__(NW * 64, 2) conv3_halo_kernel(HaloArgs g) {
     constexpr bool EDGE = WD && WN == 2 && NW == 4;
     if constexpr (WG) {
@@ -1144,8 +1152,8 @@ __global__ void __launch_bounds__(NW * 64, 2) conv3_halo_kernel(HaloArgs g) {
         t /= g.N / (NTG * 32);
         int td, th, tw;
         halo_tile_coords(g, t % (g.ntd * g.nth * g.ntw), td, th, tw);
-        if (min(g.S_out - tw * TW, g.S_out - th * TH) <= 4 && !g_dbg_all_waves(g)) conv3_halo_body<NTG, PM, NW, WD, TL, WN, 1, WG>(g);
-        else conv3_halo_body<NTG, PM, NW, WD, TL, WN, 0, WG>(g);
+        if (min(g.S_out - tw * TW, g.S_out - th * TH) <= 4 && !g_dbg_all_waves(g)) conv3_halo_body<NTG, PM, NW, WD, TL, WN, 1, WG, 0, TANH>(g);
+        else conv3_halo_body<NTG, PM, NW, WD, TL, WN, 0, WG, 0, TANH>(g);
         return;
     } else
     if constexpr (EDGE) {
@@ -1158,17 +1166,17 @@ __global__ void __launch_bounds__(NW * 64, 2) conv3_halo_kernel(HaloArgs g) {
         int td, th, tw;
         halo_tile_coords(g, t % (g.ntd * g.nth * g.ntw), td, th, tw);
         if (g.S_out - td * TD <= 2 && !g_dbg_all_waves(g)) {
-            conv3_halo_body<NTG, PM, NW, WD, TL, WN, 3>(g);
+            conv3_halo_body<NTG, PM, NW, WD, TL, WN, 3, 0, 0, TANH>(g);
             return;
         }
         const int rem = min(g.S_out - tw * TW, g.S_out - th * TH);
         if (rem <= 6 && !g_dbg_all_waves(g)) {
-            if (rem <= 4) conv3_halo_body<NTG, PM, NW, WD, TL, WN, 1>(g);
-            else conv3_halo_body<NTG, PM, NW, WD, TL, WN, 2>(g);
+            if (rem <= 4) conv3_halo_body<NTG, PM, NW, WD, TL, WN, 1, 0, 0, TANH>(g);
+            else conv3_halo_body<NTG, PM, NW, WD, TL, WN, 2, 0, 0, TANH>(g);
             return;
         }
     }
-    conv3_halo_body<NTG, PM, NW, WD, TL, WN, 0, 0, BLN>(g);
+    conv3_halo_body<NTG, PM, NW, WD, TL, WN, 0, 0, BLN, TANH>(g);
 }
 
 inline bool hb_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
@@ -1180,19 +1188,25 @@ int g_halo_wn = 0;         // experiment knob (vxb_debug_set_halo_wn): waves alo
                           // repetitions each, B = 16, S = 100): forward 20.23 -> 19.43 ms, data gradient + padding adjoint
                           // 21.89 -> 20.85 ms; the tap-list variant (up-conv data gradient) is unchanged, 11.0 ms either way        // experiment knob (vxb_debug_set_halo_waves): 4 waves x 2 M tiles or 8 waves x 1 M tile per workgroup
 
-template <int NT, int PM, int NW, int WD, int TL = 0, int WN = 1, int WG = 0, int BLN = 0>
-int hb_launch(const HaloArgs& g, long long nblk, hipStream_t st) {
+template <int NT, int PM, int NW, int WD, int TL, int WN, int WG, int BLN, bool TANH>
+int hb_launch_t(const HaloArgs& g, long long nblk, hipStream_t st) {
     // (the fold epilogue re-uses the buffer as an fp32 [256][64] tile: keep the full size in every variant)
     const size_t lds = WG == 2 ? (size_t)(8 * HHp * HW_USED * 32 + 6 * 2048) * sizeof(u16)      // compact image + the fragment ring (conv3_halo_body: BL)
                      : WG ? (size_t)8 * HHp * HWp * SP * sizeof(u16)
                      : BLN ? (size_t)(HALO_SLOTS * SP + 5 * 2048) * sizeof(u16)                   // padded image + the fragment ring (BN)
                      : (size_t)(HALO_SLOTS * SP + 2 * NT * 32 * LDW) * sizeof(u16);
     if (TL && (size_t)(g.ncls * 32 + g.nphase * 2) * sizeof(int) > (size_t)2 * NT * 32 * LDW * sizeof(u16)) return VXB_ESIZE;
-    if (hipFuncSetAttribute((const void*)conv3_halo_kernel<NT, PM, NW, WD, TL, WN, WG, BLN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)conv3_halo_kernel<NT, PM, NW, WD, TL, WN, WG, BLN, TANH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return VXB_ELAUNCH;
-    hipLaunchKernelGGL((conv3_halo_kernel<NT, PM, NW, WD, TL, WN, WG, BLN>), dim3((unsigned)(nblk * (g.N / (NT * 32)) * (TL ? g.ksplit : 1))), dim3(NW * 64), lds, st, g);
+    hipLaunchKernelGGL((conv3_halo_kernel<NT, PM, NW, WD, TL, WN, WG, BLN, TANH>), dim3((unsigned)(nblk * (g.N / (NT * 32)) * (TL ? g.ksplit : 1))), dim3(NW * 64), lds, st, g);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
+}
+// the tanh epilogues (forward: tanh, fold: tanh') are their own instantiations: the act 0 / 1 kernels keep the code they had before them
+template <int NT, int PM, int NW, int WD, int TL = 0, int WN = 1, int WG = 0, int BLN = 0>
+int hb_launch(const HaloArgs& g, long long nblk, hipStream_t st) {
+    return g.act == VXB_ACT_TANH ? hb_launch_t<NT, PM, NW, WD, TL, WN, WG, BLN, true>(g, nblk, st)
+                                 : hb_launch_t<NT, PM, NW, WD, TL, WN, WG, BLN, false>(g, nblk, st);
 }
 
 int hb_impl(int x3 /* product mode: 0 bf16, 1 bf16x3, 2 fp16 (WD kernels only, `scale` = {in, 1 / in} on the device) */, const float* src0, const float* src1, int C0, int C1, int B, int S_in, int S_out, int off, int replicate,
@@ -1270,6 +1284,7 @@ extern "C" int vxb_conv3_halo_bf16w_f32(const float* src0, const float* src1, in
                                         int off, int replicate, const void* wt_bf16, int N, const float* bias, float* out,
                                         int act, float slope, int s2d_s, int s2d_C, int d2s_s, const void* wfrag, const int32_t* taptab,
                                          int ncls, int tap_total, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     return hb_impl(0, src0, src1, C0, C1, B, S_in, S_out, off, replicate, wt_bf16, N, bias, out, act, slope, s2d_s, s2d_C, d2s_s,
                    stream, nullptr, wfrag, taptab, ncls, s2d_s * s2d_s * s2d_s, tap_total);
 }
@@ -1279,6 +1294,7 @@ extern "C" int vxb_conv3_halo_bf16x3_f32(const float* src0, const float* src1, i
                                          int off, int replicate, const void* wt_bf16, int N, const float* bias, float* out,
                                          int act, float slope, int s2d_s, int s2d_C, int d2s_s, const void* wfrag, const int32_t* taptab,
                                          int ncls, int tap_total, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     return hb_impl(1, src0, src1, C0, C1, B, S_in, S_out, off, replicate, wt_bf16, N, bias, out, act, slope, s2d_s, s2d_C, d2s_s,
                    stream, nullptr, wfrag, taptab, ncls, s2d_s * s2d_s * s2d_s, tap_total);
 }
@@ -1297,6 +1313,7 @@ extern "C" int vxb_conv3_halo_ss3d_bf16x3_f32(const float* src0, const float* sr
                                               const float* bias, float* out, int act, float slope, const void* wfrag, const float* lin,
                                               float* part_ws, float* out_ss, float* out_max, float* stats, int32_t* argmax,
                                               vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!wfrag || !lin || !part_ws || !out_ss || !out_max || !stats || !argmax) return VXB_EARG;
     const int rc = hb_impl(1, src0, src1, C0, C1, B, S, S, -1, 1, wt_bf16, 64, bias, out, act, slope, 0, 0, 0, stream, nullptr, wfrag,
                            nullptr, 0, 0, 0, nullptr, 1, nullptr, part_ws, lin);
@@ -1313,6 +1330,7 @@ extern "C" int vxb_conv3_halo_ss3d_wg_bf16x3_f32(const float* src0, const float*
                                                  float* out, int act, float slope, const void* wfrag_wg, const float* lin,
                                                  float* part_ws, float* out_ss, float* out_max, float* stats, int32_t* argmax,
                                                  vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!wfrag_wg || !lin || !part_ws || !out_ss || !out_max || !stats || !argmax || (S & 1)) return VXB_EARG;
     const int rc = hb_impl(1, src0, src1, C0, C1, B, S, S, -1, 1, wfrag_wg, 64, bias, out, act, slope, 0, 0, 0, stream, nullptr, wfrag_wg,
                            nullptr, 0, 0, 0, nullptr, 1, nullptr, part_ws, lin, 1);
@@ -1341,12 +1359,13 @@ extern "C" int vxb_conv3_s2d_splitk_f32(const float* src_fine, int C0, int B, in
 
 // Data gradient of a 3x3x3 replicate-padded conv fused with the adjoint of its padding (vxb_conv3_halo_* followed by
 // vxb_fold_pad_f32, without writing the padded-domain gradient): dy [B, S^3, C0] -> for each 64-column block nb of the
-// N <= 128 input channels, dst_nb [B, S^3, 64] (+)= fold(conv_zero_pad(dy, wt_dgrad)) (* LeakyReLU'(y_nb) when y_nb is
+// N <= 128 input channels, dst_nb [B, S^3, 64] (+)= fold(conv_zero_pad(dy, wt_dgrad)) (* the derivative of the producer's activation at y_nb -- act_bwd -- when y_nb is
 // given).  x3 != 0: weights are the [2][N][K] planes ('bf16x3').  pad = 1.
-extern "C" int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
-                                        float* dst1, const float* y0, const float* y1, int acc0, int acc1, float slope,
+extern "C" int vxb_conv3_dgrad_fold_act_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
+                                        float* dst1, const float* y0, const float* y1, int acc0, int acc1, int act, float slope,
                                         const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
                                         vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     // dst_colsum (optional, [64], ACCUMULATED; needs colsum_ws of 64 * vxb_conv3_dgrad_fold_blocks + 64 * 64 floats; N = 64 only): column
     // sums of dst0 as written (after the LeakyReLU' factor) = the bias gradient of the conv whose activation y0 is
     // dst_scale (optional, [2], needs scale_ws of vxb_conv3_dgrad_fold_blocks words; N = 64 only): the fp16 operand scale of dst0 as
@@ -1363,7 +1382,7 @@ extern "C" int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, c
     f.fold_acc[0] = acc0; f.fold_acc[1] = acc1;
     f.amax_part = dst_scale ? reinterpret_cast<unsigned*>(scale_ws) : nullptr;
     f.colsum_part = dst_colsum ? colsum_ws : nullptr;
-    int rc = hb_impl(x3 ? 1 : 0, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wt_bf16, N, nullptr, nullptr, 0, slope, 0, 0, 0, stream, &f, wfrag);
+    int rc = hb_impl(x3 ? 1 : 0, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wt_bf16, N, nullptr, nullptr, act, vxb_lrelu_slope(act, slope), 0, 0, 0, stream, &f, wfrag);
     if (rc) return rc;
     const int nblk = (int)vxb_conv3_dgrad_fold_blocks(B, S, N);
     if (dst_colsum) {
@@ -1387,7 +1406,7 @@ extern "C" size_t vxb_conv3_dgrad_fold_blocks(int B, int S, int N) {
 // gradients it is indistinguishable from the bf16x3 evaluation (tools/experiments/emu_precision.py --round4), while the d(u0)
 // half, which propagates through the whole decoder and trunk, stays bf16x3.
 static int dgrad_fold_f16(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
-                          int acc, float slope, const float* scale, vxb_stream_t stream, int wino) {
+                          int acc, int act, float slope, const float* scale, vxb_stream_t stream, int wino) {
     if (!dy || !wfrag_f16 || !dst || S < 2) return VXB_EARG;
     const int pad = 1, S_out = S + 2 * pad;
     if ((S_out - 1 - pad) / TD != (S_out - 1) / TD || (S_out - 1 - pad) / TH != (S_out - 1) / TH || (S_out - 1 - pad) / TW != (S_out - 1) / TW)
@@ -1396,20 +1415,22 @@ static int dgrad_fold_f16(const float* dy, int C0, int B, int S, const void* wfr
     f.fold_pad = pad; f.fold_S = S; f.fold_dst[0] = dst; f.fold_dst[1] = nullptr; f.fold_y[0] = y; f.fold_y[1] = nullptr;
     f.fold_acc[0] = acc; f.fold_acc[1] = 0;
     f.amax_part = nullptr; f.colsum_part = nullptr;
-    return hb_impl(2, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16, 64, nullptr, nullptr, 0, slope, 0, 0, 0, stream, &f,
+    return hb_impl(2, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16, 64, nullptr, nullptr, act, vxb_lrelu_slope(act, slope), 0, 0, 0, stream, &f,
                    wfrag_f16, nullptr, 0, 0, 0, scale, 1, nullptr, nullptr, nullptr, wino);
 }
 
-extern "C" int vxb_conv3_dgrad_fold_f16_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
-                                            int acc, float slope, const float* scale, vxb_stream_t stream) {
-    return dgrad_fold_f16(dy, C0, B, S, wfrag_f16, dst, y, acc, slope, scale, stream, 0);
+extern "C" int vxb_conv3_dgrad_fold_f16_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
+                                            int acc, int act, float slope, const float* scale, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
+    return dgrad_fold_f16(dy, C0, B, S, wfrag_f16, dst, y, acc, act, slope, scale, stream, 0);
 }
 // ... with the depth axis by Winograd's F(2, 3): wfrag = ops.halo_wfrag_x2_wg (the 36 transformed taps in fp16, 16-channel chunks);
 // S even.  See vxb_conv3_dgrad_fold_f16x2_wg_f32.
-extern "C" int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
-                                               int acc, float slope, const float* scale, vxb_stream_t stream) {
+extern "C" int vxb_conv3_dgrad_fold_f16_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
+                                               int acc, int act, float slope, const float* scale, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if ((S & 1) || !scale) return VXB_EARG;
-    return dgrad_fold_f16(dy, C0, B, S, wfrag_f16_wg, dst, y, acc, slope, scale, stream, 1);
+    return dgrad_fold_f16(dy, C0, B, S, wfrag_f16_wg, dst, y, acc, act, slope, scale, stream, 1);
 }
 
 // One 64-column block of the data gradient + padding adjoint on TWO fp16 products per term ("fp16x2": dy * scale[0] as an fp16
@@ -1418,7 +1439,7 @@ extern "C" int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, i
 // vxb_conv3_dgrad_fold_f32 (operand scale of dst, column sums of dst).  Against the reference's gradients the weight rounding of a
 // data gradient moves no gate (tools/experiments/emu_precision.py --round5), and a third of the MFMAs is gone.
 static int dgrad_fold_f16x2(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
-                            int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
+                            int acc, int act, float slope, const float* scale, float* dst_scale, float* scale_ws,
                             float* dst_colsum, float* colsum_ws, vxb_stream_t stream, int wino) {
     if (!dy || !wfrag_f16x2 || !dst || !scale || S < 2) return VXB_EARG;
     if ((dst_scale && !scale_ws) || (dst_colsum && !colsum_ws)) return VXB_EARG;
@@ -1430,7 +1451,7 @@ static int dgrad_fold_f16x2(const float* dy, int C0, int B, int S, const void* w
     f.fold_acc[0] = acc; f.fold_acc[1] = 0;
     f.amax_part = dst_scale ? reinterpret_cast<unsigned*>(scale_ws) : nullptr;
     f.colsum_part = dst_colsum ? colsum_ws : nullptr;
-    int rc = hb_impl(3, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16x2, 64, nullptr, nullptr, 0, slope, 0, 0, 0, stream, &f,
+    int rc = hb_impl(3, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16x2, 64, nullptr, nullptr, act, vxb_lrelu_slope(act, slope), 0, 0, 0, stream, &f,
                      wfrag_f16x2, nullptr, 0, 0, 0, scale, 1, nullptr, nullptr, nullptr, wino);
     if (rc) return rc;
     const int nblk = (int)vxb_conv3_dgrad_fold_blocks(B, S, 64);
@@ -1442,18 +1463,20 @@ static int dgrad_fold_f16x2(const float* dy, int C0, int B, int S, const void* w
     return vxb_absmax_finish_launch(f.amax_part, nblk, dst_scale, (hipStream_t)stream);
 }
 
-extern "C" int vxb_conv3_dgrad_fold_f16x2_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
-                                              int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
+extern "C" int vxb_conv3_dgrad_fold_f16x2_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
+                                              int acc, int act, float slope, const float* scale, float* dst_scale, float* scale_ws,
                                               float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
-    return dgrad_fold_f16x2(dy, C0, B, S, wfrag_f16x2, dst, y, acc, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream, 0);
+    if (!vxb_act_ok(act)) return VXB_EARG;
+    return dgrad_fold_f16x2(dy, C0, B, S, wfrag_f16x2, dst, y, acc, act, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream, 0);
 }
 // ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_halo_ss3d_wg_bf16x3_f32): wfrag = ops.halo_wfrag_x2_wg, the 36
 // transformed taps rounded to fp16 AFTER the transform; S even.
-extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
-                                                 const float* y, int acc, float slope, const float* scale, float* dst_scale,
+extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
+                                                 const float* y, int acc, int act, float slope, const float* scale, float* dst_scale,
                                                  float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (S & 1) return VXB_EARG;
-    return dgrad_fold_f16x2(dy, C0, B, S, wfrag_f16x2_wg, dst, y, acc, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream, 1);
+    return dgrad_fold_f16x2(dy, C0, B, S, wfrag_f16x2_wg, dst, y, acc, act, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream, 1);
 }
 
 // The same launch when the 64-column block is the data gradient of a 1x1x1 conv's OUTPUT y [B, S^3, 64] = lrelu(W_in x + b_in) whose
@@ -1461,9 +1484,10 @@ extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B,
 // feeds dW_in [64][10] / db_in [64], so it is not stored -- the epilogue multiplies it with LeakyReLU'(y) and the voxel's inputs and the
 // sums are ACCUMULATED into dW / db (4.1 GB less written here, 4.1 GB less read by vxb_pointwise_wgrad_ss3d_f32).
 // ws: 704 * (vxb_conv3_dgrad_fold_blocks(B, S, 64) + 512) floats.
-extern "C" int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
-                                                 const float* x, float slope, const float* scale, float* ws, float* dW, float* db,
+extern "C" int vxb_conv3_dgrad_fold_f16_wgin_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
+                                                 const float* x, int act, float slope, const float* scale, float* ws, float* dW, float* db,
                                                  vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!dy || !wfrag_f16 || !y || !x || !scale || !ws || !dW || !db || S < 2) return VXB_EARG;
     if ((((uintptr_t)x) & 7) || (((uintptr_t)y) & 15)) return VXB_ESIZE;
     const int pad = 1, S_out = S + 2 * pad;
@@ -1473,8 +1497,39 @@ extern "C" int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B,
     f.fold_pad = pad; f.fold_S = S; f.fold_dst[0] = ws /* (never written in this mode) */; f.fold_dst[1] = ws;
     f.fold_y[0] = y; f.fold_y[1] = x; f.fold_acc[0] = 0; f.fold_acc[1] = 2;          // "wgin": see HaloArgs
     f.amax_part = nullptr; f.colsum_part = nullptr;
-    int rc = hb_impl(2, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16, 64, nullptr, nullptr, 0, slope, 0, 0, 0, stream, &f,
+    int rc = hb_impl(2, dy, nullptr, C0, 0, B, S, S_out, -2 * pad, 0, wfrag_f16, 64, nullptr, nullptr, act, vxb_lrelu_slope(act, slope), 0, 0, 0, stream, &f,
                      wfrag_f16, nullptr, 0, 0, 0, scale);
     if (rc) return rc;
     return vxb_wgin_finish_launch(ws, (int)vxb_conv3_dgrad_fold_blocks(B, S, 64), scale, dW, db, (hipStream_t)stream);
+}
+
+// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
+extern "C" int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
+                                        float* dst1, const float* y0, const float* y1, int acc0, int acc1, float slope,
+                                        const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
+                                        vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_act_f32(dy, C0, B, S, wt_bf16, x3, N, dst0, dst1, y0, y1, acc0, acc1, VXB_ACT_LRELU, slope, wfrag, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
+}
+extern "C" int vxb_conv3_dgrad_fold_f16_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
+                                            int acc, float slope, const float* scale, vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_f16_act_f32(dy, C0, B, S, wfrag_f16, dst, y, acc, VXB_ACT_LRELU, slope, scale, stream);
+}
+extern "C" int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
+                                               int acc, float slope, const float* scale, vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_f16_wg_act_f32(dy, C0, B, S, wfrag_f16_wg, dst, y, acc, VXB_ACT_LRELU, slope, scale, stream);
+}
+extern "C" int vxb_conv3_dgrad_fold_f16x2_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
+                                              int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
+                                              float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_f16x2_act_f32(dy, C0, B, S, wfrag_f16x2, dst, y, acc, VXB_ACT_LRELU, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
+}
+extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
+                                                 const float* y, int acc, float slope, const float* scale, float* dst_scale,
+                                                 float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_f16x2_wg_act_f32(dy, C0, B, S, wfrag_f16x2_wg, dst, y, acc, VXB_ACT_LRELU, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
+}
+extern "C" int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
+                                                 const float* x, float slope, const float* scale, float* ws, float* dW, float* db,
+                                                 vxb_stream_t stream) {
+    return vxb_conv3_dgrad_fold_f16_wgin_act_f32(dy, C0, B, S, wfrag_f16, y, x, VXB_ACT_LRELU, slope, scale, ws, dW, db, stream);
 }

@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(G256Args g) {
                 const int m = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (m >= g.M) continue;
                 float v = acc[i][j][r] + bsv;
-                if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd(v, g.act, g.slope);
                 const long long off = (long long)m * g.ldc + n;
                 if (R) v += R[off];
                 if (g.accumulate) v += C[off];
@@ -170,6 +170,7 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(G256Args g) {
 extern "C" int vxb_gemm256_f32(const void* A_planes, int64_t lda, const void* W_planes, int nplanes, float* C, int64_t ldc,
                                const float* bias, const float* residual, int M, int N, int K, int act, float slope, int accumulate,
                                vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A_planes || !W_planes || !C || M < 1 || N < 1 || K < BK || (K % BK) || (nplanes != 1 && nplanes != 2)) return VXB_EARG;
     if ((lda & 7) || (((uintptr_t)A_planes) & 15) || (((uintptr_t)W_planes) & 15)) return VXB_EARG;
     G256Args g;

@@ -356,7 +356,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g) {
                 const int m = m0 + wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m >= g.M) continue;
                 float v = g.alpha * acc[i][j][r] + bsv;
-                if (g.act == ACT_LRELU) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd(v, g.act, g.slope);
                 long long off;
                 if (g.d2s_s > 0) {
                     const int s = g.d2s_s, G = g.d2s_G, Cc = g.d2s_C;
@@ -417,6 +417,7 @@ extern "C" int vxb_gemm_f32(const float* A, const float* B, float* C, const floa
                             int M, int N, int K, int64_t sAm, int64_t sAk, int64_t sBk, int64_t sBn, int64_t ldc,
                             int batch, int H, int64_t bA1, int64_t bA2, int64_t bB1, int64_t bB2, int64_t bC1,
                             int64_t bC2, float alpha, int act, float slope, int accumulate, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A || !B || !C || M < 1 || N < 1 || K < 1 || batch < 1 || H < 1) return VXB_EARG;
     if (!aligned16(A) || !aligned16(B)) return VXB_EARG;
     GemmArgs g = {};
@@ -448,6 +449,7 @@ extern "C" int vxb_conv3d_f32(const float* src0, const float* src1, int C0, int 
                               int stride, int kext, int off, int replicate, const float* wt, int N,
                               const float* bias, float* out, int64_t ldc, int act, float slope, int accumulate,
                               int d2s_s, int d2s_C, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!src0 || !wt || !out || B < 1 || S_in < 1 || S_out < 1 || kext < 1 || stride < 1 || N < 1) return VXB_EARG;
     if ((C0 & 15) || (C1 & 15) || C0 < 16 || (C1 > 0 && !src1)) return VXB_ESIZE;
     if ((N & 3) || !aligned16(src0) || !aligned16(wt) || (src1 && !aligned16(src1))) return VXB_ESIZE;
@@ -753,7 +755,7 @@ __global__ void __launch_bounds__(256) gemm_bf16_kernel(GemmArgs g, const u16* _
                 const int m = m0 + wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m >= g.M) continue;
                 float v = g.alpha * acc[i][j][r] + bsv;
-                if (g.act == ACT_LRELU) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd(v, g.act, g.slope);
                 long long off;
                 if (g.d2s_s > 0) {
                     const int s = g.d2s_s, G = g.d2s_G, Cc = g.d2s_C;
@@ -799,6 +801,7 @@ int launch_gemm_bf16(const GemmArgs& g, const u16* Bw, hipStream_t st) {
 extern "C" int vxb_gemm_bf16w_f32(const float* A, int64_t lda, const void* Bw, float* C, int64_t ldc, const float* bias,
                                   const float* residual, int M, int N, int K, int act, float slope, int accumulate,
                                   vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A || !Bw || !C || M < 1 || N < 1 || K < 8) return VXB_EARG;
     if ((K & 7) || (lda & 3) || !aligned16(A) || !aligned16(Bw)) return VXB_ESIZE;
     GemmArgs g = {};
@@ -811,6 +814,7 @@ extern "C" int vxb_gemm_bf16w_f32(const float* A, int64_t lda, const void* Bw, f
 extern "C" int vxb_gemm_bf16x3_f32(const float* A, int64_t lda, const void* Bw, float* C, int64_t ldc, const float* bias,
                                    const float* residual, int M, int N, int K, int act, float slope, int accumulate,
                                    vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A || !Bw || !C || M < 1 || N < 1 || K < 8) return VXB_EARG;
     if ((K & 7) || (lda & 3) || !aligned16(A) || !aligned16(Bw)) return VXB_ESIZE;
     GemmArgs g = {};
@@ -824,6 +828,7 @@ static int conv3d_bf16_impl(int x3, const float* src0, const float* src1, int C0
                            int stride, int kext, int off, int replicate, const void* wt_bf16, int N,
                            const float* bias, float* out, int64_t ldc, int act, float slope, int accumulate,
                            int d2s_s, int d2s_C, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!src0 || !wt_bf16 || !out || B < 1 || S_in < 1 || S_out < 1 || kext < 1 || stride < 1 || N < 1) return VXB_EARG;
     if ((C0 & 31) || (C1 & 31) || C0 < 32 || (C1 > 0 && !src1)) return VXB_ESIZE;
     if (!aligned16(src0) || !aligned16(wt_bf16) || (src1 && !aligned16(src1))) return VXB_ESIZE;

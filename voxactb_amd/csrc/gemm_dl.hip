@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(256, 2) gemm_dl_kernel(DlArgs g) {
                 for (int j = 0; j < TN; ++j) {
                     if (!cok[j]) continue;
                     float v = acc[i][j][r] + bsv[j];
-                    if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                    v = act_fwd(v, g.act, g.slope);
                     const long long off = rowoff + coloff[j];
                     if (R) v += R[off];
                     if (g.accumulate) v += C[off];
@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(256, 2) gemm_dl_kernel(DlArgs g) {
                 const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m >= g.M) continue;
                 float v = acc[i][j][r] + bsv;
-                if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd(v, g.act, g.slope);
                 const long long off = (long long)m * g.ldc + n;
                 if (R) v += R[off];
                 if (g.accumulate) v += C[off];
@@ -542,6 +542,7 @@ extern "C" int vxb_split_bf16_batch_f32(const int64_t* desc, int n, int64_t tota
 extern "C" int vxb_gemm_dl_f32(const void* A_planes, const void* Bw_planes, const void* Bw_frag, int nplanes, float* C, int64_t ldc,
                                const float* bias, const float* residual, int M, int N, int K, int act, float slope,
                                int accumulate, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A_planes || !Bw_planes || !C || M < 1 || N < 1 || K < 32 || (nplanes != 1 && nplanes != 2)) return VXB_EARG;
     if ((K & 31) || !dl_al16(A_planes) || !dl_al16(Bw_planes)) return VXB_ESIZE;
     if (Bw_frag && !dl_al16(Bw_frag)) return VXB_ESIZE;
@@ -565,6 +566,7 @@ extern "C" int vxb_conv3d_dl_f32(const void* src_planes, int Cin, int B, int S_i
                                  int replicate, const void* wt_planes, const void* wt_frag, int nplanes, int N, const float* bias, float* out,
                                  int64_t ldc, int act, float slope, int accumulate, int d2s_s, int d2s_C, const void* zeros,
                                  const uint32_t* tapmask, const int32_t* d2s_perm, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!src_planes || !wt_planes || !out || !zeros || B < 1 || S_in < 1 || S_out < 1 || kext < 1 || stride < 1 || N < 1) return VXB_EARG;
     if ((nplanes != 1 && nplanes != 2) || (Cin & 31) || Cin < 32) return VXB_ESIZE;
     if (!dl_al16(src_planes) || !dl_al16(wt_planes) || !dl_al16(zeros)) return VXB_ESIZE;

@@ -70,7 +70,7 @@ __device__ __forceinline__ f32x16 gw_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
 // NW = 8: one workgroup of 8 waves per CU owns 128 x 512; NW = 4: 128 x 256 per workgroup of 4 waves, TWO workgroups per CU (one wave of
 // each per SIMD), so that one workgroup's barrier, prologue and epilogue stores run under the other's MFMAs.  The column groups of a row
 // block get consecutive virtual block ids on the same XCD (A comes out of that XCD's L2 for all but the first).
-template <int X2, int NW>
+template <int X2, int NW, bool TANH>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_wide_kernel(GwArgs g) {
     __shared__ __attribute__((aligned(16))) u16 As[2][2][WBM * WLD];          // [stage][plane]: 40 KB
     const int tid = threadIdx.x, lane = tid & 63;
@@ -323,10 +323,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_wide_kernel(GwA
                     if (m >= g.M) continue;
                     float4 v = *reinterpret_cast<const float4*>(&Cs[row * CLD + ec]);
                     v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w;
-                    if (g.act == 1) {
-                        v.x = v.x > 0.f ? v.x : v.x * g.slope; v.y = v.y > 0.f ? v.y : v.y * g.slope;
-                        v.z = v.z > 0.f ? v.z : v.z * g.slope; v.w = v.w > 0.f ? v.w : v.w * g.slope;
-                    }
+                    v.x = act_fwd_t<TANH>(v.x, g.act, g.slope); v.y = act_fwd_t<TANH>(v.y, g.act, g.slope);
+                    v.z = act_fwd_t<TANH>(v.z, g.act, g.slope); v.w = act_fwd_t<TANH>(v.w, g.act, g.slope);
                     const long long off = (long long)m * g.ldc + n4;
                     if (R) { const float4 q = *reinterpret_cast<const float4*>(R + off); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
                     if (g.accumulate) { const float4 q = *reinterpret_cast<const float4*>(C + off); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
@@ -387,7 +385,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_wide_kernel(GwA
                 const int m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m >= g.M) continue;
                 float v = (X2 ? acc[i][j][r] * out_sc : acc[i][j][r]) + bsv;
-                if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd_t<TANH>(v, g.act, g.slope);
                 const long long off = (long long)m * g.ldc + n;
                 if (R) v += R[off];
                 if (g.accumulate) v += C[off];
@@ -425,6 +423,7 @@ struct PwArgs {
     int dbg;                 // vxb_debug_set_gemm_wide_experiment bit 64: the epilogue of rounds 4 - 5 (stores straight out of the accumulators)
 };
 
+template <bool TANH>
 __global__ void __launch_bounds__(512) conv_poly_wide_x3_kernel(PwArgs g) {
     __shared__ __attribute__((aligned(16))) u16 As[2][2][WBM * WLD];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -628,10 +627,8 @@ __global__ void __launch_bounds__(512) conv_poly_wide_x3_kernel(PwArgs g) {
                     const int qd = q % g.S; q /= g.S;
                     float4 v = *reinterpret_cast<const float4*>(&Ws[row * 64 + ec]);
                     v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w;
-                    if (g.act == 1) {
-                        v.x = v.x > 0.f ? v.x : v.x * g.slope; v.y = v.y > 0.f ? v.y : v.y * g.slope;
-                        v.z = v.z > 0.f ? v.z : v.z * g.slope; v.w = v.w > 0.f ? v.w : v.w * g.slope;
-                    }
+                    v.x = act_fwd_t<TANH>(v.x, g.act, g.slope); v.y = act_fwd_t<TANH>(v.y, g.act, g.slope);
+                    v.z = act_fwd_t<TANH>(v.z, g.act, g.slope); v.w = act_fwd_t<TANH>(v.w, g.act, g.slope);
                     *reinterpret_cast<float4*>(g.out + ((((long long)q * Vf + qd * sfac + rd) * Vf + qh * sfac + rh) * Vf + qw * sfac + rw) * 64 + ec) = v;
                 }
             }
@@ -652,7 +649,7 @@ __global__ void __launch_bounds__(512) conv_poly_wide_x3_kernel(PwArgs g) {
             for (int j = 0; j < 2; ++j) {
                 const int co = j * 32 + (lane & 31);
                 float v = acc[i][j][r] + (g.bias ? g.bias[blk * 64 + co] : 0.f);
-                if (g.act == 1) v = v > 0.f ? v : v * g.slope;
+                v = act_fwd_t<TANH>(v, g.act, g.slope);
                 op[co] = v;
             }
         }
@@ -660,21 +657,27 @@ __global__ void __launch_bounds__(512) conv_poly_wide_x3_kernel(PwArgs g) {
 }
 
 int g_wide_waves = 8, g_wide_dbg = 0;
-template <int X2>
-void gw_launch(GwArgs& g, int M, int N, hipStream_t stream) {
+template <int X2, bool TANH>
+void gw_launch_t(GwArgs& g, int M, int N, hipStream_t stream) {
     g.dbg = g_wide_dbg; g.N_total = N;
     if (g_wide_waves == 4) {
         g.ncg = N / 256;
-        hipLaunchKernelGGL((gemm_wide_kernel<X2, 4>), dim3(vxb_cdiv(M, WBM) * g.ncg), dim3(256), 0, stream, g);
+        hipLaunchKernelGGL((gemm_wide_kernel<X2, 4, TANH>), dim3(vxb_cdiv(M, WBM) * g.ncg), dim3(256), 0, stream, g);
     } else if (N > 512 && !(g_wide_dbg & 32)) {
         // the column groups of a row block on adjacent workgroups of one XCD: A out of that XCD's L2, C rows written side by side
         // (4096 x 512: 0.55-0.60 -> 0.52-0.54 ms)
         g.ncg = N / 512;
-        hipLaunchKernelGGL((gemm_wide_kernel<X2, 8>), dim3(vxb_cdiv(M, WBM) * g.ncg), dim3(512), 0, stream, g);
+        hipLaunchKernelGGL((gemm_wide_kernel<X2, 8, TANH>), dim3(vxb_cdiv(M, WBM) * g.ncg), dim3(512), 0, stream, g);
     } else {
         g.ncg = 0;
-        hipLaunchKernelGGL((gemm_wide_kernel<X2, 8>), dim3(vxb_cdiv(M, WBM), N / 512), dim3(512), 0, stream, g);
+        hipLaunchKernelGGL((gemm_wide_kernel<X2, 8, TANH>), dim3(vxb_cdiv(M, WBM), N / 512), dim3(512), 0, stream, g);
     }
+}
+// the tanh epilogue is its own instantiation (the act 0 / 1 kernels keep the code they had before it existed)
+template <int X2>
+void gw_launch(GwArgs& g, int M, int N, hipStream_t stream) {
+    if (g.act == VXB_ACT_TANH) gw_launch_t<X2, true>(g, M, N, stream);
+    else gw_launch_t<X2, false>(g, M, N, stream);
 }
 
 }  // namespace
@@ -688,6 +691,7 @@ extern "C" void vxb_debug_set_gemm_wide_experiment(int bits) { g_wide_dbg = bits
 extern "C" int vxb_gemm_wide_bf16x3_f32(const float* A, int64_t lda, const void* Bw_frag, float* C, int64_t ldc, const float* bias,
                                         const float* residual, int M, int N, int K, int act, float slope, int accumulate,
                                         vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A || !Bw_frag || !C || M < 1 || K < 64) return VXB_EARG;
     if (N < 512 || (N & 511) || (K & 31) || (lda & 3) || (((uintptr_t)A | (uintptr_t)Bw_frag) & 15)) return VXB_ESIZE;
     GwArgs g;
@@ -704,6 +708,7 @@ extern "C" int vxb_gemm_wide_bf16x3_f32(const float* A, int64_t lda, const void*
 extern "C" int vxb_gemm_wide_bf16x3_f16out_f32(const float* A, int64_t lda, const void* Bw_frag, float* C, int64_t ldc, const float* bias,
                                                const float* residual, int M, int N, int K, int act, float slope, int accumulate,
                                                void* f16_out, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!A || !Bw_frag || !C || !f16_out || M < 1 || K < 64) return VXB_EARG;
     if (N < 512 || (N & 511) || (K & 31) || (lda & 3) || (((uintptr_t)A | (uintptr_t)Bw_frag | (uintptr_t)f16_out) & 15)) return VXB_ESIZE;
     GwArgs g;
@@ -788,6 +793,7 @@ extern "C" int vxb_gemm_wide_geglu_bwd_f16x2_f32(const float* dY, int64_t lda, c
 extern "C" int vxb_conv3_poly_wide_bf16x3_f32(const float* z, int Cin, int B, int S, int kext, int off, int replicate,
                                               const void* wt_frag, int N, const float* bias, float* out, int act, float slope,
                                               int d2s_s, const int32_t* blockmask, const int32_t* perm, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!z || !wt_frag || !out || !blockmask || B < 1 || S < 1 || kext < 1 || N < 64 || d2s_s < 1) return VXB_EARG;
     if ((Cin & 31) || Cin < 32 || (N & 63) || kext * kext * kext > 32 || (((uintptr_t)z | (uintptr_t)wt_frag) & 15)) return VXB_ESIZE;
     const long long M = (long long)B * S * S * S;
@@ -795,7 +801,10 @@ extern "C" int vxb_conv3_poly_wide_bf16x3_f32(const float* z, int Cin, int B, in
     PwArgs g;
     g.z = z; g.Bfrag = (const u16*)wt_frag; g.bias = bias; g.out = out; g.perm = perm; g.blockmask = blockmask;
     g.B = B; g.S = S; g.Cin = Cin; g.kext = kext; g.off = off; g.replicate = replicate; g.N = N; g.s = d2s_s; g.act = act; g.slope = slope; g.dbg = g_wide_dbg;
-    hipLaunchKernelGGL(conv_poly_wide_x3_kernel, dim3((unsigned)vxb_cdiv(M, WBM), vxb_cdiv(N, 512)), dim3(512), 0, (hipStream_t)stream, g);
+    if (act == VXB_ACT_TANH)
+        hipLaunchKernelGGL(conv_poly_wide_x3_kernel<true>, dim3((unsigned)vxb_cdiv(M, WBM), vxb_cdiv(N, 512)), dim3(512), 0, (hipStream_t)stream, g);
+    else
+        hipLaunchKernelGGL(conv_poly_wide_x3_kernel<false>, dim3((unsigned)vxb_cdiv(M, WBM), vxb_cdiv(N, 512)), dim3(512), 0, (hipStream_t)stream, g);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }

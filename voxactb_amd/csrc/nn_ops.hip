@@ -510,9 +510,9 @@ __global__ void __launch_bounds__(256) geglu_bwd_kernel(const float* __restrict_
     }
 }
 __global__ void __launch_bounds__(256) lrelu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
-                                                        float* __restrict__ dx, long long n, float slope) {
+                                                        float* __restrict__ dx, long long n, int act, float slope) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        dx[i] = y[i] > 0.f ? dy[i] : dy[i] * slope;
+        dx[i] = act_bwd(dy[i], y[i], act, slope);
 }
 __global__ void __launch_bounds__(256) add_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n, float alpha) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] += alpha * src[i];
@@ -530,7 +530,7 @@ __global__ void __launch_bounds__(256) naive_gemm_kernel(const float* __restrict
         float s = 0.f;
         for (int k = 0; k < K; ++k) s = fmaf(A[m * sAm + k * sAk], B[k * sBk + n * sBn], s);
         if (bias) s += bias[n];
-        if (act == 1) s = s > 0.f ? s : s * slope;
+        s = act_fwd(s, act, slope);
         if (accumulate) C[m * ldc + n] += s; else C[m * ldc + n] = s;
     }
 }
@@ -560,7 +560,7 @@ __global__ void __launch_bounds__(256) naive_gemm_wave_kernel(const float* __res
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if (lane == 0) {
             if (bias) s += bias[n];
-            if (act == 1) s = s > 0.f ? s : s * slope;
+            s = act_fwd(s, act, slope);
             if (accumulate) C[m * ldc + n] += s; else C[m * ldc + n] = s;
         }
     }
@@ -887,11 +887,14 @@ extern "C" int vxb_geglu_bwd_f32(const float* h, const float* dout, float* dh, i
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
-extern "C" int vxb_lrelu_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, float slope, vxb_stream_t stream) {
-    if (!dy || !y || !dx || n < 1) return VXB_EARG;
-    hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, (long long)n, slope);
+extern "C" int vxb_lrelu_bwd_act_f32(const float* dy, const float* y, float* dx, int64_t n, int act, float slope, vxb_stream_t stream) {
+    if (!dy || !y || !dx || n < 1 || !vxb_act_ok(act)) return VXB_EARG;
+    hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dx, (long long)n, act, slope);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
+}
+extern "C" int vxb_lrelu_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, float slope, vxb_stream_t stream) {
+    return vxb_lrelu_bwd_act_f32(dy, y, dx, n, VXB_ACT_LRELU, slope, stream);
 }
 extern "C" int vxb_axpy_f32(float* dst, const float* src, int64_t n, float alpha, vxb_stream_t stream) {
     if (!dst || !src || n < 1) return VXB_EARG;
@@ -902,7 +905,7 @@ extern "C" int vxb_axpy_f32(float* dst, const float* src, int64_t n, float alpha
 extern "C" int vxb_naive_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K,
                                   int64_t sAm, int64_t sAk, int64_t sBk, int64_t sBn, int64_t ldc, int act, float slope,
                                   int accumulate, vxb_stream_t stream) {
-    if (!A || !B || !C || M < 1 || N < 1 || K < 1) return VXB_EARG;
+    if (!A || !B || !C || M < 1 || N < 1 || K < 1 || !vxb_act_ok(act)) return VXB_EARG;
     if ((long long)M * N <= 16384 && K >= 128)
         hipLaunchKernelGGL(naive_gemm_wave_kernel, dim3((unsigned)(((long long)M * N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, A, B, C, bias,
                            M, N, K, (long long)sAm, (long long)sAk, (long long)sBk, (long long)sBn, (long long)ldc, act, slope, accumulate);

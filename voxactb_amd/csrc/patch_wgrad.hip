@@ -37,18 +37,20 @@ constexpr int PCIN = 10;             // channels of the voxel grid
 struct PgArgs {
     const float* dpatch;     // [B, G^3, 64] fp32 (after the patchify block's LeakyReLU')
     const u16* wt;           // fp16 [k^3][64 c][64 kout]: Wp[kout][c][tap] transposed per tap (ops.patch_dgrad_weights)
-    const float* d0;         // [B, V^3, 64] output of the input conv (its sign = LeakyReLU')
+    const float* d0;         // [B, V^3, 64] output of the input conv (act_bwd reads the derivative of its activation from it)
     const float* vox;        // [B, V^3, 10]
     const float* scale;      // {s, 1 / s}: dpatch is multiplied by s before the conversion to half
     float* part;             // [k^3 * Z][64][11] partial sums (scaled by s)
     float* wpart;            // optional: [k^3][Z][64 c][64 kout] partial sums of the patchify weight gradient (scaled by s)
     int B, V, G, k, pad, Z;
+    int act;                 // activation of the input conv (common.h act_bwd on d0)
     float slope;
     unsigned magic;          // floor(2^32 / G) + 1: p / G == __umulhi(p, magic) for p * G < 2^32 (host-checked)
 };
 
 constexpr int TLD = 36;             // u16 per row of the transposed dpatch tile (32 patches + 4 pad: 18 dwords, conflict-free b64 column reads)
 
+template <bool TANH>
 __global__ void __launch_bounds__(256, 2) patch_wgrad_kernel(PgArgs g) {
     __shared__ float wred[4][32][33];
     __shared__ __attribute__((aligned(8))) u16 tdp[4][64 * TLD];      // per wave: this step's dpatch tile as fp16 [kout][patch]
@@ -150,7 +152,7 @@ __global__ void __launch_bounds__(256, 2) patch_wgrad_kernel(PgArgs g) {
                 const float y = g.d0[v * 64 + 32 * j + lm];
                 yk[j][r] = y;
                 float d = live ? acc[j][r] : 0.f;
-                d = y > 0.f ? d : d * g.slope;
+                d = act_bwd_t<TANH>(d, y, g.slope);
                 // 2^-4 of headroom: dpatch arrives scaled to max |dpatch| < 2^15 (ops: the operand scale of this launch) and G sums 64 products
                 // with patchify weights, so |G| < 2^15 * 64 * max|W| -- below 65504 * 16 for max|W| < 0.5 (the released weights: 0.09); beyond
                 // that vxb_sat_f16 clips the operand of dW_in | db (tests/test_patch_wgrad_gpu.py provokes it and checks the bound stated there)
@@ -308,22 +310,31 @@ extern "C" size_t vxb_patch_wgrad_weight_ws_floats(int k, int nsplit) { return (
 // ws: vxb_patch_dgrad_input_wgrad_ws_floats(k, nsplit) floats.  dWp (optional, with ws_wp of vxb_patch_wgrad_weight_ws_floats(k, nsplit)
 // floats): the patchify weight gradient [64 kout][64 c][k^3] in the parameter's own layout, ACCUMULATED, from the same pass over d0
 // (network_utils.py:128-170 backward; single fp16 products).
-extern "C" int vxb_patch_dgrad_input_wgrad_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V,
-                                               int G, int k, int pad, float slope, const float* scale, float* ws, int nsplit,
+extern "C" int vxb_patch_dgrad_input_wgrad_act_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V,
+                                               int G, int k, int pad, int act, float slope, const float* scale, float* ws, int nsplit,
                                                float* dW, float* db, float* dWp, float* ws_wp, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!dpatch || !wt_f16 || !d0 || !vox || !scale || !ws || !dW || !db || B < 1 || V < 1 || G < 1 || k < 1 || nsplit < 1) return VXB_EARG;
     if ((((uintptr_t)dpatch | (uintptr_t)wt_f16) & 15) || (((uintptr_t)vox) & 7) || nsplit > 65535) return VXB_ESIZE;
     if ((long long)B * V * V * V >= INT32_MAX || (long long)B * G * G * G * G >= (1ll << 32) || G < 2) return VXB_ESIZE;
     PgArgs g;
     g.magic = (unsigned)((1ull << 32) / (unsigned)G) + 1u;
     g.dpatch = dpatch; g.wt = (const u16*)wt_f16; g.d0 = d0; g.vox = vox; g.scale = scale; g.part = ws;
-    g.B = B; g.V = V; g.G = G; g.k = k; g.pad = pad; g.Z = nsplit; g.slope = slope;
+    g.B = B; g.V = V; g.G = G; g.k = k; g.pad = pad; g.Z = nsplit; g.act = act; g.slope = vxb_lrelu_slope(act, slope);
     if ((dWp != nullptr) != (ws_wp != nullptr)) return VXB_EARG;
     g.wpart = ws_wp;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(patch_wgrad_kernel, dim3(k * k * k, nsplit), dim3(256), 0, st, g);
+    if (act == VXB_ACT_TANH) hipLaunchKernelGGL(patch_wgrad_kernel<true>, dim3(k * k * k, nsplit), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(patch_wgrad_kernel<false>, dim3(k * k * k, nsplit), dim3(256), 0, st, g);
     if (dWp)
         hipLaunchKernelGGL(patch_wgrad_weight_finish_kernel, dim3(vxb_cdiv((long long)k * k * k * 4096, 256)), dim3(256), 0, st, ws_wp, k * k * k, nsplit,
                            scale, dWp);
     return vxb_wgin_finish_launch(ws, k * k * k * nsplit, scale, dW, db, st);
+}
+
+// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
+extern "C" int vxb_patch_dgrad_input_wgrad_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V,
+                                               int G, int k, int pad, float slope, const float* scale, float* ws, int nsplit,
+                                               float* dW, float* db, float* dWp, float* ws_wp, vxb_stream_t stream) {
+    return vxb_patch_dgrad_input_wgrad_act_f32(dpatch, wt_f16, d0, vox, B, V, G, k, pad, VXB_ACT_LRELU, slope, scale, ws, nsplit, dW, db, dWp, ws_wp, stream);
 }

@@ -18,11 +18,12 @@ inline int grid_for(long long n) {
 }
 
 // =====================================================================================================
-// pointwise conv  y[v, co] = lrelu(sum_ci x[v, ci] * W[co, ci] + b[co]),  Cin <= 16, Cout % 4 == 0, Cout <= 128
+// pointwise conv  y[v, co] = act(sum_ci x[v, ci] * W[co, ci] + b[co]),  Cin <= 16, Cout % 4 == 0, Cout <= 128
 // =====================================================================================================
+template <bool TANH>
 __global__ void __launch_bounds__(256) pw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                      const float* __restrict__ bias, float* __restrict__ y,
-                                                     long long nvox, int Cin, int Cout, float slope) {
+                                                     long long nvox, int Cin, int Cout, int act, float slope) {
     __shared__ float sw[16 * 128];     // [ci][co]
     __shared__ float sb[128];
     for (int i = threadIdx.x; i < Cin * Cout; i += 256) {
@@ -44,8 +45,8 @@ __global__ void __launch_bounds__(256) pw_fwd_kernel(const float* __restrict__ x
             a0 = fmaf(xv, wr[0], a0); a1 = fmaf(xv, wr[1], a1); a2 = fmaf(xv, wr[2], a2); a3 = fmaf(xv, wr[3], a3);
         }
         float4 o;
-        o.x = a0 > 0.f ? a0 : a0 * slope; o.y = a1 > 0.f ? a1 : a1 * slope;
-        o.z = a2 > 0.f ? a2 : a2 * slope; o.w = a3 > 0.f ? a3 : a3 * slope;
+        o.x = lrelu_or_tanh<TANH>(a0, slope); o.y = lrelu_or_tanh<TANH>(a1, slope);
+        o.z = lrelu_or_tanh<TANH>(a2, slope); o.w = lrelu_or_tanh<TANH>(a3, slope);
         *reinterpret_cast<float4*>(y + v * Cout + c4) = o;
     }
 }
@@ -54,7 +55,7 @@ __global__ void __launch_bounds__(256) pw_fwd_kernel(const float* __restrict__ x
 __global__ void __launch_bounds__(256) pw_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ dy, float* __restrict__ partW,
                                                        float* __restrict__ partB, long long nvox, int Cin, int vox_per_block,
-                                                       float slope) {
+                                                       int act, float slope) {
     __shared__ float red[256 * 17];
     const int co = threadIdx.x & 63, grp = threadIdx.x >> 6;
     float acc[16], accb = 0.f;
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(256) pw_wgrad_kernel(const float* __restrict__
     for (long long v = v0 + grp; v < v1; v += 4) {
         const float yv = y[v * 64 + co];
         float d = dy[v * 64 + co];
-        d = yv > 0.f ? d : d * slope;
+        d = act_bwd(d, yv, act, slope);
         accb += d;
         const float* xr = x + v * Cin;
 #pragma unroll
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(256) pw_wgrad_kernel(const float* __restrict__
 __global__ void __launch_bounds__(256) pw_wgrad4_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                         const float* __restrict__ dy, float* __restrict__ partW,
                                                         float* __restrict__ partB, long long nvox, int Cin, int vox_per_block,
-                                                        float slope) {
+                                                        int act, float slope) {
     __shared__ float red[4][64 * 17];
     const int c4 = (threadIdx.x & 15) * 4, gl = threadIdx.x >> 4, wid = threadIdx.x >> 6;
     float acc[4][16], accb[4];
@@ -118,8 +119,8 @@ __global__ void __launch_bounds__(256) pw_wgrad4_kernel(const float* __restrict_
         }
 #pragma unroll
         for (int uu = 0; uu < 2; ++uu) {
-            const float d[4] = {yy[uu].x > 0.f ? dd[uu].x : dd[uu].x * slope, yy[uu].y > 0.f ? dd[uu].y : dd[uu].y * slope,
-                                yy[uu].z > 0.f ? dd[uu].z : dd[uu].z * slope, yy[uu].w > 0.f ? dd[uu].w : dd[uu].w * slope};
+            const float d[4] = {act_bwd(dd[uu].x, yy[uu].x, act, slope), act_bwd(dd[uu].y, yy[uu].y, act, slope),
+                                act_bwd(dd[uu].z, yy[uu].z, act, slope), act_bwd(dd[uu].w, yy[uu].w, act, slope)};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 accb[e] += d[e];
@@ -280,10 +281,10 @@ __global__ void __launch_bounds__(256) ss_part4_kernel(const float* __restrict__
 // A (d, h) row of x (S voxels x CIN floats, contiguous) is staged in LDS by the whole workgroup, one row ahead: the 16 threads
 // that share a voxel read its CIN inputs as LDS broadcasts instead of 16 x CIN global loads.
 constexpr int PWSS_MAX_S = 256;
-template <int CIN>
+template <int CIN, bool TANH>
 __global__ void __launch_bounds__(256) pw_fwd_ss_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                         const float* __restrict__ bias, float* __restrict__ y, int S,
-                                                        float slope, const float* __restrict__ lin, int rows_per_chunk,
+                                                        int act, float slope, const float* __restrict__ lin, int rows_per_chunk,
                                                         SsPart* __restrict__ part, int nchunk, float T) {
     __shared__ SsPart red[256 * 4];
     __shared__ float sx[2][PWSS_MAX_S * CIN];
@@ -352,8 +353,8 @@ __global__ void __launch_bounds__(256) pw_fwd_ss_kernel(const float* __restrict_
                     a0 = fmaf(xv, wreg[ci][0], a0); a1 = fmaf(xv, wreg[ci][1], a1);
                     a2 = fmaf(xv, wreg[ci][2], a2); a3 = fmaf(xv, wreg[ci][3], a3);
                 }
-                o[uu].x = a0 > 0.f ? a0 : a0 * slope; o[uu].y = a1 > 0.f ? a1 : a1 * slope;
-                o[uu].z = a2 > 0.f ? a2 : a2 * slope; o[uu].w = a3 > 0.f ? a3 : a3 * slope;
+                o[uu].x = lrelu_or_tanh<TANH>(a0, slope); o[uu].y = lrelu_or_tanh<TANH>(a1, slope);
+                o[uu].z = lrelu_or_tanh<TANH>(a2, slope); o[uu].w = lrelu_or_tanh<TANH>(a3, slope);
                 if (ok) *reinterpret_cast<float4*>(yb + (long long)(row * S + k) * C) = o[uu];
             }
             const int p0 = row * S + k0;
@@ -535,10 +536,10 @@ __global__ void __launch_bounds__(256) ss_bwd_kernel(const float* __restrict__ x
 // LEAN (dy == nullptr and fold_src == nullptr: every conv path into y adds its share of dW / db itself, the shape the training step
 // takes): only y is streamed, EIGHT voxels ahead instead of two -- the kernel moved 4.3 GB in 2.18 ms (2 TB/s) with 32 KB per CU in
 // flight; it is bound by memory latency, not by its arithmetic (profiles/r05_*: 56 % of the wave time in s_waitcnt).
-template <int CIN, int MODE>           // MODE 1: LEAN; 2: y and dy, no fold_src (the default training step): four voxels in flight; 0: generic
+template <int CIN, int MODE, bool TANH>           // MODE 1: LEAN; 2: y and dy, no fold_src (the default training step): four voxels in flight; 0: generic
 __global__ void __launch_bounds__(256) pw_wgrad4_ss_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ dy, float* __restrict__ partW,
-                                                           float* __restrict__ partB, int S, int vox_per_block, float slope,
+                                                           float* __restrict__ partB, int S, int vox_per_block, int act, float slope,
                                                            const float* __restrict__ lin, const float* __restrict__ stats,
                                                            const float* __restrict__ out_ss, const int* __restrict__ argmax,
                                                            const float* __restrict__ g_ss, const float* __restrict__ g_max, float T,
@@ -663,7 +664,7 @@ __global__ void __launch_bounds__(256) pw_wgrad4_ss_kernel(const float* __restri
                         float g = divT(a * ((gx[e] * (lj - ex[e]) + gy[e] * (li - ey[e])) + gz[e] * (lk - ez[e])));
                         if (p == am[e]) g += gm[e];
                         float d = ds[e] + g;
-                        d = ys[e] > 0.f ? d : d * slope;
+                        d = act_bwd_t<TANH>(d, ys[e], slope);
                         accb[e] += d;
 #pragma unroll
                         for (int ci = 0; ci < CIN; ++ci) acc[e][ci] = fmaf(d, xr[ci], acc[e][ci]);
@@ -759,7 +760,7 @@ __global__ void __launch_bounds__(256) c1_fwd_kernel(const float* __restrict__ u
 // per axis, pair k in {0,1,2}: o = j + 1 - k, t = k; o < 0 -> (0, t=0); o > S-1 -> (S-1, t=2)   (replicate adjoint)
 __global__ void __launch_bounds__(256) c1_dgrad_kernel(const float* __restrict__ dq, const float* __restrict__ w,
                                                        const float* __restrict__ u, float* __restrict__ du, int B, int S,
-                                                       int accumulate, int mask, float slope) {
+                                                       int accumulate, int mask, int act, float slope) {
     const int lane = threadIdx.x & 63;
     __shared__ float sw[27 * 64];          // [t][c]: runtime tap index at the borders -> LDS, not registers
     for (int i = threadIdx.x; i < 27 * 64; i += 256) sw[(i % 27) * 64 + i / 27] = w[i];
@@ -791,7 +792,7 @@ __global__ void __launch_bounds__(256) c1_dgrad_kernel(const float* __restrict__
                 }
         const long long o = v * 64 + lane;
         float r = acc + (accumulate ? du[o] : 0.f);
-        if (mask) r = u[o] > 0.f ? r : r * slope;
+        if (mask) r = act_bwd(r, u[o], act, slope);
         du[o] = r;
     }
 }
@@ -860,7 +861,7 @@ __global__ void __launch_bounds__(256) c1_wgrad_kernel(const float* __restrict__
 // =====================================================================================================
 __global__ void __launch_bounds__(256) fold_kernel(const float* __restrict__ src, int Sp, int Cs, int c0,
                                                    float* __restrict__ dst, const float* __restrict__ y, int B, int S, int C,
-                                                   int pad, int accumulate, float slope) {
+                                                   int pad, int accumulate, int act, float slope) {
     const int q = C >> 2;
     const long long total = (long long)B * S * S * S * q;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -888,8 +889,8 @@ __global__ void __launch_bounds__(256) fold_kernel(const float* __restrict__ src
         }
         if (y) {
             const float4 yy = *reinterpret_cast<const float4*>(y + o);
-            a.x = yy.x > 0.f ? a.x : a.x * slope; a.y = yy.y > 0.f ? a.y : a.y * slope;
-            a.z = yy.z > 0.f ? a.z : a.z * slope; a.w = yy.w > 0.f ? a.w : a.w * slope;
+            a.x = act_bwd(a.x, yy.x, act, slope); a.y = act_bwd(a.y, yy.y, act, slope);
+            a.z = act_bwd(a.z, yy.z, act, slope); a.w = act_bwd(a.w, yy.w, act, slope);
         }
         *reinterpret_cast<float4*>(dst + o) = a;
     }
@@ -1174,30 +1175,33 @@ extern "C" int vxb_adam_step_f32(float* w, const float* g, float* m, float* v, i
     return VXB_OK;
 }
 
-extern "C" int vxb_pointwise_fwd_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
-                                     int Cout, float slope, vxb_stream_t stream) {
+extern "C" int vxb_pointwise_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
+                                     int Cout, int act, float slope, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!x || !W || !bias || !y || nvox < 1 || Cin < 1 || Cin > 16 || Cout < 4 || Cout > 128 || (Cout & 3)) return VXB_EARG;
-    hipLaunchKernelGGL(pw_fwd_kernel, dim3(grid_for(nvox * (Cout / 4))), dim3(256), 0, (hipStream_t)stream, x, W, bias, y,
-                       (long long)nvox, Cin, Cout, slope);
+    auto kern = act == VXB_ACT_TANH ? pw_fwd_kernel<true> : pw_fwd_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(nvox * (Cout / 4))), dim3(256), 0, (hipStream_t)stream, x, W, bias, y,
+                       (long long)nvox, Cin, Cout, act, vxb_lrelu_slope(act, slope));
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
 // part_ws: nblk*(64*Cin + 64) floats with nblk = ceil(nvox / 4096).  dW [64][Cin] and db [64] are ACCUMULATED.
-extern "C" int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
-                                       int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream);
+extern "C" int vxb_pointwise_wgrad_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
+                                       int64_t nvox, int Cin, int Cout, int act, float slope, vxb_stream_t stream);
 extern "C" int vxb_sum_splits_f32(const float* part, int nsplit, int64_t n, float* dst, int accumulate, float alpha, vxb_stream_t stream);
 
-extern "C" int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
-                                       int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream) {
+extern "C" int vxb_pointwise_wgrad_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
+                                       int64_t nvox, int Cin, int Cout, int act, float slope, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!x || !y || !dy || !dW || !db || !part_ws || nvox < 1 || Cin < 1 || Cin > 16 || Cout != 64) return VXB_EARG;
     const int vpb = 4096;
     const int nb = vxb_cdiv(nvox, vpb);
     float* pW = part_ws;
     float* pB = part_ws + (size_t)nb * 64 * Cin;
     if (((((uintptr_t)y) | ((uintptr_t)dy)) & 15) == 0)
-        hipLaunchKernelGGL(pw_wgrad4_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, (long long)nvox, Cin, vpb, slope);
+        hipLaunchKernelGGL(pw_wgrad4_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, (long long)nvox, Cin, vpb, act, slope);
     else
-        hipLaunchKernelGGL(pw_wgrad_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, (long long)nvox, Cin, vpb, slope);
+        hipLaunchKernelGGL(pw_wgrad_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, (long long)nvox, Cin, vpb, act, slope);
     VXB_CHECK_LAUNCH();
     int rc = vxb_sum_splits_f32(pW, nb, 64 * Cin, dW, 1, 1.0f, stream);
     if (rc) return rc;
@@ -1269,14 +1273,15 @@ extern "C" int vxb_ss3d_max_bwd_f32(const float* x, int64_t bs, int B, int S, in
 // Fused forms for the first layer (C = 64 output channels): the input conv + LeakyReLU with the SpatialSoftmax3D / max-pool
 // statistics of its output taken while the output is written, and the conv's parameter gradients with the pooled features'
 // backward term added to dy on the fly.  Same results as the two-kernel paths (forward: bit-identical).
-extern "C" int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
-                                          float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
+extern "C" int vxb_pointwise_ss3d_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
+                                          int act, float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
                                           int32_t* argmax, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!x || !W || !bias || !y || !lin || !part_ws || !out_ss || !out_max || !stats || !argmax || B < 1 || S < 1 || Cin < 1 ||
         Cin > 16) return VXB_EARG;
     if (Cout != 64 || (((uintptr_t)y) & 15)) return VXB_ESIZE;
     if (Cin != 10 || S > PWSS_MAX_S) {          // other shapes: the two kernels one after the other (same results)
-        const int rc = vxb_pointwise_fwd_f32(x, W, bias, y, (int64_t)B * S * S * S, Cin, Cout, slope, stream);
+        const int rc = vxb_pointwise_fwd_act_f32(x, W, bias, y, (int64_t)B * S * S * S, Cin, Cout, act, slope, stream);
         if (rc) return rc;
         return vxb_ss3d_max_fwd_f32(y, (int64_t)S * S * S * 64, B, S, 64, lin, part_ws, out_ss, out_max, stats, argmax, stream);
     }
@@ -1284,8 +1289,12 @@ extern "C" int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const 
     const int want = vxb_ss3d_chunks(B);
     const int rpc = (S * S / want) < 1 ? 1 : S * S / want;
     const int nchunk = vxb_cdiv(S * S, rpc);
-    hipLaunchKernelGGL(pw_fwd_ss_kernel<10>, dim3(nchunk, B), dim3(256), 0, st, x, W, bias, y, S, slope, lin, rpc, (SsPart*)part_ws,
-                       nchunk, 0.01f);
+    if (act == VXB_ACT_TANH)
+        hipLaunchKernelGGL((pw_fwd_ss_kernel<10, true>), dim3(nchunk, B), dim3(256), 0, st, x, W, bias, y, S, act, vxb_lrelu_slope(act, slope), lin, rpc, (SsPart*)part_ws,
+                           nchunk, 0.01f);
+    else
+        hipLaunchKernelGGL((pw_fwd_ss_kernel<10, false>), dim3(nchunk, B), dim3(256), 0, st, x, W, bias, y, S, act, vxb_lrelu_slope(act, slope), lin, rpc, (SsPart*)part_ws,
+                           nchunk, 0.01f);
     if (nchunk > 128)
         hipLaunchKernelGGL(ss_final_wide_kernel, dim3(B * 64), dim3(256), 0, st, (const SsPart*)part_ws, nchunk, B, 64, 64, 0, out_ss,
                            out_max, stats, argmax, (long long)nchunk * 64, (long long)64, 1LL);
@@ -1299,10 +1308,11 @@ extern "C" int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const 
 // voxel features: 3 + 3 + 3 + 1) -- other widths return VXB_ESIZE and the caller uses the two separate kernels.
 // fold_src (or null): [B, Sp^3, 64], a data gradient on the replicate-padded domain (S + 2 pad valid per axis) whose padding
 // adjoint (vxb_fold_pad_f32) is gathered and added to dy on the fly as well.
-extern "C" int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
-                                            int S, int Cin, int Cout, float slope, const float* lin, const float* stats,
+extern "C" int vxb_pointwise_wgrad_ss3d_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
+                                            int S, int Cin, int Cout, int act, float slope, const float* lin, const float* stats,
                                             const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
                                             const float* fold_src, int Sp, int pad, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!x || !y || !dW || !db || !part_ws || !lin || !stats || !out_ss || !argmax || !g_ss || !g_max || B < 1 || S < 1 ||
         Cin < 1 || Cin > 16 || (fold_src && (pad < 0 || Sp < S + 2 * pad))) return VXB_EARG;
     if (Cout != 64 || Cin != 10 || S > 1024 || ((((uintptr_t)y) | ((uintptr_t)dy) | ((uintptr_t)fold_src)) & 15)) return VXB_ESIZE;
@@ -1311,12 +1321,15 @@ extern "C" int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, cons
     const int nb = nbs * B;
     float* pW = part_ws;
     float* pB = part_ws + (size_t)nb * 64 * Cin;
-#define PW_WG(MODE_) hipLaunchKernelGGL((pw_wgrad4_ss_kernel<10, MODE_>), dim3(nbs, B), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, S, vpb, slope, \
+    slope = vxb_lrelu_slope(act, slope);
+#define PW_WG(MODE_) do { if (act == VXB_ACT_TANH) PW_WG_T(MODE_, true); else PW_WG_T(MODE_, false); } while (0)
+#define PW_WG_T(MODE_, TANH_) hipLaunchKernelGGL((pw_wgrad4_ss_kernel<10, MODE_, TANH_>), dim3(nbs, B), dim3(256), 0, (hipStream_t)stream, x, y, dy, pW, pB, S, vpb, act, slope, \
                                         lin, stats, out_ss, argmax, g_ss, g_max, 0.01f, fold_src, Sp, pad)
     if (!dy && !fold_src) PW_WG(1);
     else if (!fold_src) PW_WG(2);
     else PW_WG(0);
 #undef PW_WG
+#undef PW_WG_T
     VXB_CHECK_LAUNCH();
     int rc = vxb_sum_splits_f32(pW, nb, 64 * Cin, dW, 1, 1.0f, stream);
     if (rc) return rc;
@@ -1334,14 +1347,15 @@ extern "C" int vxb_conv3_c1_fwd_f32(const float* u, const float* w, const float*
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
-extern "C" int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                                      int accumulate, int apply_lrelu_mask, float slope, vxb_stream_t stream) {
+extern "C" int vxb_conv3_c1_dgrad_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
+                                      int accumulate, int apply_lrelu_mask, int act, float slope, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!dq || !w || !du || (apply_lrelu_mask && !u) || B < 1 || S < 1) return VXB_EARG;
     if (C != 64) return VXB_ESIZE;
-    if ((S & 3) == 0) return vxb_c1_dgrad4_launch(dq, w, u, du, B, S, accumulate, apply_lrelu_mask, slope, (hipStream_t)stream);
+    if ((S & 3) == 0) return vxb_c1_dgrad4_launch(dq, w, u, du, B, S, accumulate, apply_lrelu_mask, act, slope, (hipStream_t)stream);
     const long long nvox = (long long)B * S * S * S;
     const int grid = (int)((nvox + 3) / 4 > 32768 ? 32768 : (nvox + 3) / 4);
-    hipLaunchKernelGGL(c1_dgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dq, w, u, du, B, S, accumulate, apply_lrelu_mask, slope);
+    hipLaunchKernelGGL(c1_dgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dq, w, u, du, B, S, accumulate, apply_lrelu_mask, act, slope);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
@@ -1351,17 +1365,18 @@ extern "C" int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const flo
 extern "C" size_t vxb_conv3_c1_dgrad_ss3d_ws_floats(int B, int S) {
     return ((size_t)vxb_c1_dgrad_ss_blocks_per_sample(S) * (size_t)B + 64) * 65;      // (+ one |du| maximum per block)
 }
-extern "C" int vxb_conv3_c1_dgrad_ss3d_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                                           int accumulate, float slope, const float* lin, const float* stats, const float* out_ss,
+extern "C" int vxb_conv3_c1_dgrad_ss3d_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
+                                           int accumulate, int act, float slope, const float* lin, const float* stats, const float* out_ss,
                                            const int32_t* argmax, const float* g_ss, const float* g_max, float* dbias,
                                            float* part_ws, float* du_scale, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!dq || !w || !u || !du || !lin || !stats || !out_ss || !argmax || !g_ss || !g_max || !dbias || !part_ws || B < 1 || S < 4)
         return VXB_EARG;
     if (C != 64 || (S & 3) || ((((uintptr_t)u) | ((uintptr_t)du)) & 15)) return VXB_ESIZE;
     // du_scale (optional, [2]): the fp16 operand scale of du (as vxb_absmax_scale_f32 would compute it), taken while du is written
     const int nb = vxb_c1_dgrad_ss_blocks_per_sample(S) * B;
     unsigned* part_amax = du_scale ? reinterpret_cast<unsigned*>(part_ws + ((size_t)nb + 64) * 64) : nullptr;
-    int rc = vxb_c1_dgrad4_ss_launch(dq, w, u, du, B, S, accumulate, slope, lin, stats, out_ss, argmax, g_ss, g_max, dbias, part_ws,
+    int rc = vxb_c1_dgrad4_ss_launch(dq, w, u, du, B, S, accumulate, act, slope, lin, stats, out_ss, argmax, g_ss, g_max, dbias, part_ws,
                                      part_amax, (hipStream_t)stream);
     if (rc || !du_scale) return rc;
     return vxb_absmax_finish_launch(part_amax, nb, du_scale, (hipStream_t)stream);
@@ -1383,11 +1398,12 @@ extern "C" int vxb_conv3_c1_wgrad_f32(const float* u, const float* dq, float* dw
     return vxb_sum_splits_f32(pB, nb, 1, db, 1, 1.0f, stream);
 }
 
-extern "C" int vxb_fold_pad_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
-                                int C, int pad, int accumulate, float slope, vxb_stream_t stream) {
+extern "C" int vxb_fold_pad_act_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
+                                int C, int pad, int accumulate, int act, float slope, vxb_stream_t stream) {
+    if (!vxb_act_ok(act)) return VXB_EARG;
     if (!src || !dst || B < 1 || S < 1 || C < 4 || (C & 3) || (Cs & 3) || (c0 & 3) || pad < 0 || Sp < S + 2 * pad) return VXB_EARG;
     hipLaunchKernelGGL(fold_kernel, dim3(grid_for((long long)B * S * S * S * (C / 4))), dim3(256), 0, (hipStream_t)stream, src, Sp, Cs,
-                       c0, dst, lrelu_of, B, S, C, pad, accumulate, slope);
+                       c0, dst, lrelu_of, B, S, C, pad, accumulate, act, slope);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
@@ -1485,4 +1501,39 @@ extern "C" int vxb_se3_points_f32(const float* src, float* dst, const float* xf,
     hipLaunchKernelGGL(se3_points_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, src, dst, xf, (long long)n);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
+}
+
+// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
+extern "C" int vxb_pointwise_fwd_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
+                                     int Cout, float slope, vxb_stream_t stream) {
+    return vxb_pointwise_fwd_act_f32(x, W, bias, y, nvox, Cin, Cout, VXB_ACT_LRELU, slope, stream);
+}
+extern "C" int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
+                                       int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream) {
+    return vxb_pointwise_wgrad_act_f32(x, y, dy, dW, db, part_ws, nvox, Cin, Cout, VXB_ACT_LRELU, slope, stream);
+}
+extern "C" int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
+                                          float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
+                                          int32_t* argmax, vxb_stream_t stream) {
+    return vxb_pointwise_ss3d_fwd_act_f32(x, W, bias, y, B, S, Cin, Cout, VXB_ACT_LRELU, slope, lin, part_ws, out_ss, out_max, stats, argmax, stream);
+}
+extern "C" int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
+                                            int S, int Cin, int Cout, float slope, const float* lin, const float* stats,
+                                            const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
+                                            const float* fold_src, int Sp, int pad, vxb_stream_t stream) {
+    return vxb_pointwise_wgrad_ss3d_act_f32(x, y, dy, dW, db, part_ws, B, S, Cin, Cout, VXB_ACT_LRELU, slope, lin, stats, out_ss, argmax, g_ss, g_max, fold_src, Sp, pad, stream);
+}
+extern "C" int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
+                                      int accumulate, int apply_lrelu_mask, float slope, vxb_stream_t stream) {
+    return vxb_conv3_c1_dgrad_act_f32(dq, w, u, du, B, S, C, accumulate, apply_lrelu_mask, VXB_ACT_LRELU, slope, stream);
+}
+extern "C" int vxb_conv3_c1_dgrad_ss3d_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
+                                           int accumulate, float slope, const float* lin, const float* stats, const float* out_ss,
+                                           const int32_t* argmax, const float* g_ss, const float* g_max, float* dbias,
+                                           float* part_ws, float* du_scale, vxb_stream_t stream) {
+    return vxb_conv3_c1_dgrad_ss3d_act_f32(dq, w, u, du, B, S, C, accumulate, VXB_ACT_LRELU, slope, lin, stats, out_ss, argmax, g_ss, g_max, dbias, part_ws, du_scale, stream);
+}
+extern "C" int vxb_fold_pad_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
+                                int C, int pad, int accumulate, float slope, vxb_stream_t stream) {
+    return vxb_fold_pad_act_f32(src, Sp, Cs, c0, dst, lrelu_of, B, S, C, pad, accumulate, VXB_ACT_LRELU, slope, stream);
 }

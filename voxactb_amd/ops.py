@@ -10,7 +10,19 @@ from . import _lib
 from ._lib import call
 
 LRELU_SLOPE = 0.02   # reference: peract/helpers/network_utils.py:12
-ACT_NONE, ACT_LRELU = 0, 1
+ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
+# an engine's activation descriptor (code, slope) per encoder `activation` (include/voxactb_hip.h, "Activation codes"; ReLU is
+# LeakyReLU with slope 0 in both directions).  Every op that applies an activation or its derivative takes `act` as such a pair,
+# or as a bare code, which means the reference's LeakyReLU slope.
+ACTIVATIONS = {'lrelu': (ACT_LRELU, LRELU_SLOPE), 'relu': (ACT_LRELU, 0.0), 'tanh': (ACT_TANH, 0.0)}
+LRELU = ACTIVATIONS['lrelu']
+
+
+def _act(act):
+    """-> (code, slope) for the kernels' `int act, float slope` arguments"""
+    if isinstance(act, tuple):
+        return int(act[0]), float(act[1])
+    return int(act), LRELU_SLOPE
 _NAIVE_MACS = 1 << 22
 
 # Compute precision of the matrix-core kernels, set by PerceiverEngine per call (its default is bf16x3):
@@ -262,12 +274,12 @@ def gemm(A, B, C, M, N, K, sAm, sAk, sBk, sBn, ldc, bias=None, residual=None, ba
     _f32c(A, B, C, bias, residual)
     _lib.set_meta(label or 'gemm', 2.0 * M * N * K * batch)
     call('vxb_gemm_f32', A, B, C, bias, residual, M, N, K, sAm, sAk, sBk, sBn, ldc, batch, H,
-         bA[0], bA[1], bB[0], bB[1], bC[0], bC[1], float(alpha), act, LRELU_SLOPE, int(accumulate))
+         bA[0], bA[1], bB[0], bB[1], bC[0], bC[1], float(alpha), *_act(act), int(accumulate))
 
 
 def naive_gemm(A, B, C, M, N, K, sAm, sAk, sBk, sBn, ldc, bias=None, act=ACT_NONE, accumulate=False):
     _f32c(A, B, C, bias)
-    call('vxb_naive_gemm_f32', A, B, C, bias, M, N, K, sAm, sAk, sBk, sBn, ldc, act, LRELU_SLOPE, int(accumulate))
+    call('vxb_naive_gemm_f32', A, B, C, bias, M, N, K, sAm, sAk, sBk, sBn, ldc, *_act(act), int(accumulate))
 
 
 def _small(M, N, K):
@@ -521,8 +533,9 @@ def geglu_bwd(h, dout):
     return dh
 
 
-def lrelu_bwd_(dy, y):
-    call('vxb_lrelu_bwd_f32', dy, y, dy, dy.numel(), LRELU_SLOPE)
+def lrelu_bwd_(dy, y, act=LRELU):
+    """dy *= the derivative of the activation `act` (a descriptor, ACTIVATIONS) read from its output y"""
+    call('vxb_lrelu_bwd_act_f32', dy, y, dy, dy.numel(), *_act(act))
     return dy
 
 
@@ -570,7 +583,7 @@ def conv3d(src0, wt, N, B, S_in, S_out, kext, off, stride=1, replicate=True, bia
     _lib.set_meta(label or 'conv3d[k%d s%d %d->%d S%d%s]' % (kext, stride, C0 + C1, N, S_out, '' if replicate else ' dgrad'),
                   2.0 * B * S_out ** 3 * N * kext ** 3 * (C0 + C1))
     call('vxb_conv3d_f32', src0, src1, C0, C1, B, S_in, S_out, stride, kext, off, int(replicate), wt, N, bias, out,
-         ldc if ldc is not None else N, act, LRELU_SLOPE, int(accumulate), d2s[0], d2s[1])
+         ldc if ldc is not None else N, *_act(act), int(accumulate), d2s[0], d2s[1])
     return out
 
 
@@ -715,8 +728,9 @@ def k5_shift_rows(dev):
     return t
 
 
-def fold_pad(src, Sp, Cs, c0, dst, B, S, C, pad, accumulate=False, lrelu_of=None):
-    call('vxb_fold_pad_f32', src, Sp, Cs, c0, dst, lrelu_of, B, S, C, pad, int(accumulate), LRELU_SLOPE)
+def fold_pad(src, Sp, Cs, c0, dst, B, S, C, pad, accumulate=False, lrelu_of=None, act=LRELU):
+    """lrelu_of: the output of the activation `act` whose derivative multiplies the result"""
+    call('vxb_fold_pad_act_f32', src, Sp, Cs, c0, dst, lrelu_of, B, S, C, pad, int(accumulate), *_act(act))
     return dst
 
 
@@ -883,14 +897,14 @@ def conv3_polyphase_fwd(z, Weff, Cout, B, G, k, s, bias, act=ACT_NONE, label=Non
             wt = Weff.t().view(s ** 3, Cout, K).index_select(0, st['perm8_long']).view(N, K)
             wf = gemm_wfrag(split_planes(wt, npl))
         _lib.set_meta(lbl, 2.0 * B * G ** 3 * N * kl ** 3 * C * st['frac'])
-        call('vxb_conv3_poly_wide_bf16x3_f32', z, C, B, G, kl, -R, 1, wf, N, bias, out, act, LRELU_SLOPE, s, st['block_mask8'], st['perm8'])
+        call('vxb_conv3_poly_wide_bf16x3_f32', z, C, B, G, kl, -R, 1, wf, N, bias, out, *_act(act), s, st['block_mask8'], st['perm8'])
         return out
     wt = Weff.t().view(s ** 3, Cout, K).index_select(0, st['perm_long']).view(N, K)      # [(phase in tile order, co)][K]
     wb = split_planes(wt, npl)
     _lib.set_meta(lbl, 0.0)
     planes = split_planes(z.reshape(-1, C), npl)
     _lib.set_meta(lbl, 2.0 * B * G ** 3 * N * kl ** 3 * C * st['frac'])
-    call('vxb_conv3d_dl_f32', planes, C, B, G, G, 1, kl, -R, 1, wb, gemm_wfrag(wb), npl, N, bias, out, N, act, LRELU_SLOPE, 0, s, Cout,
+    call('vxb_conv3d_dl_f32', planes, C, B, G, G, 1, kl, -R, 1, wb, gemm_wfrag(wb), npl, N, bias, out, N, *_act(act), 0, s, Cout,
          _zeros16(z.device), st['tile_mask'], st['perm'])
     return out
 
@@ -937,7 +951,7 @@ def dgrad_fold_ok(C_dy, N, S):
 
 
 def conv3_dgrad_fold(dy, wt_dgrad, B, S, N, dsts, label=None, dy_scale=None, leaf_blocks=(), scale_blocks=(), colsum_into=None,
-                     wgin=None):
+                     wgin=None, act=LRELU):
     """fold_pad(conv3d(dy, wt_dgrad, zero pad, S+2), pad=1) without the padded tensor: dsts = [(dst [B,S,S,S,64],
     accumulate, lrelu_of or None)] per 64-column block (1 or 2 entries).
     leaf_blocks: the column blocks whose result only feeds a weight gradient (nothing propagates from them); with
@@ -948,7 +962,8 @@ def conv3_dgrad_fold(dy, wt_dgrad, B, S, N, dsts, label=None, dy_scale=None, lea
     pre-activation gradient of) -- from the epilogue on the split path, by a colsum pass otherwise.
     wgin {block: (y, x, dW, db)} (leaf blocks on the fp16 path only; see wgin_fold_ok): the block is the data gradient of y = lrelu(1x1x1
     conv of the detached x [B,S,S,S,10]); instead of being stored to its dst (which may then be None) it is multiplied with
-    LeakyReLU'(y) and x in the epilogue and dW [64][10] / db [64] are accumulated."""
+    LeakyReLU'(y) and x in the epilogue and dW [64][10] / db [64] are accumulated.  act: the activation (descriptor) whose outputs the
+    lrelu_of / y tensors are -- every derivative above is that activation's."""
     C0 = dy.shape[-1]
     wb = to_bf16_nk(wt_dgrad)
     x3 = wb.dim() == 3
@@ -971,8 +986,8 @@ def conv3_dgrad_fold(dy, wt_dgrad, B, S, N, dsts, label=None, dy_scale=None, lea
                     sc = absmax_scale(dy)
                 if LEAF_WINOGRAD and S % 2 == 0 and not (wgin and nb in wgin):
                     _lib.set_meta(lbl, flops / len(dsts))
-                    call('vxb_conv3_dgrad_fold_f16_wg_f32', dy, C0, B, S, halo_wfrag_x2_wg(wt_dgrad[:, 64 * nb:64 * nb + 64], C0), dst, yv,
-                         int(acc), LRELU_SLOPE, sc)
+                    call('vxb_conv3_dgrad_fold_f16_wg_act_f32', dy, C0, B, S, halo_wfrag_x2_wg(wt_dgrad[:, 64 * nb:64 * nb + 64], C0), dst, yv,
+                         int(acc), *_act(act), sc)
                     continue
                 w16 = wt_dgrad[:, 64 * nb:64 * nb + 64].t().contiguous().half()           # [64][27 C0]
                 wf16 = halo_wfrag(w16, C0)
@@ -980,9 +995,9 @@ def conv3_dgrad_fold(dy, wt_dgrad, B, S, N, dsts, label=None, dy_scale=None, lea
                 if wgin and nb in wgin:
                     yw, xw, dWw, dbw = wgin[nb]
                     ws = torch.empty(704 * (int(_lib.lib().vxb_conv3_dgrad_fold_blocks(B, S, 64)) + 512), dtype=torch.float32, device=dy.device)
-                    call('vxb_conv3_dgrad_fold_f16_wgin_f32', dy, C0, B, S, wf16, yw, xw, LRELU_SLOPE, sc, ws, dWw, dbw)
+                    call('vxb_conv3_dgrad_fold_f16_wgin_act_f32', dy, C0, B, S, wf16, yw, xw, *_act(act), sc, ws, dWw, dbw)
                     continue
-                call('vxb_conv3_dgrad_fold_f16_f32', dy, C0, B, S, wf16, dst, yv, int(acc), LRELU_SLOPE, sc)
+                call('vxb_conv3_dgrad_fold_f16_act_f32', dy, C0, B, S, wf16, dst, yv, int(acc), *_act(act), sc)
             else:
                 dsc = sws = cs = cws = None
                 nblk = int(_lib.lib().vxb_conv3_dgrad_fold_blocks(B, S, 64))
@@ -998,18 +1013,18 @@ def conv3_dgrad_fold(dy, wt_dgrad, B, S, N, dsts, label=None, dy_scale=None, lea
                         sc = absmax_scale(dy)
                     _lib.set_meta(lbl, flops / len(dsts))
                     if DGRAD_WINOGRAD and S % 2 == 0:
-                        call('vxb_conv3_dgrad_fold_f16x2_wg_f32', dy, C0, B, S, halo_wfrag_x2_wg(wt_dgrad[:, 64 * nb:64 * nb + 64], C0), dst, yv,
-                             int(acc), LRELU_SLOPE, sc, dsc, sws, cs, cws)
+                        call('vxb_conv3_dgrad_fold_f16x2_wg_act_f32', dy, C0, B, S, halo_wfrag_x2_wg(wt_dgrad[:, 64 * nb:64 * nb + 64], C0), dst, yv,
+                             int(acc), *_act(act), sc, dsc, sws, cs, cws)
                         continue
                     wf2 = halo_wfrag_x2(wt_dgrad[:, 64 * nb:64 * nb + 64].t().contiguous().half(), C0)
-                    call('vxb_conv3_dgrad_fold_f16x2_f32', dy, C0, B, S, wf2, dst, yv, int(acc), LRELU_SLOPE, sc, dsc, sws, cs, cws)
+                    call('vxb_conv3_dgrad_fold_f16x2_act_f32', dy, C0, B, S, wf2, dst, yv, int(acc), *_act(act), sc, dsc, sws, cs, cws)
                     continue
                 _lib.set_meta(lbl, flops / len(dsts))
-                call('vxb_conv3_dgrad_fold_f32', dy, C0, B, S, wb, 1, 64, dst, None, yv, None, int(acc), 0, LRELU_SLOPE, wf[nb:nb + 1],
+                call('vxb_conv3_dgrad_fold_act_f32', dy, C0, B, S, wb, 1, 64, dst, None, yv, None, int(acc), 0, *_act(act), wf[nb:nb + 1],
                      dsc, sws, cs, cws)
         return scales
     _lib.set_meta(lbl, flops)
-    call('vxb_conv3_dgrad_fold_f32', dy, C0, B, S, wb, int(x3), N, d0, d1, y0, y1, int(a0), int(a1), LRELU_SLOPE, wf, None, None, None, None)
+    call('vxb_conv3_dgrad_fold_act_f32', dy, C0, B, S, wb, int(x3), N, d0, d1, y0, y1, int(a0), int(a1), *_act(act), wf, None, None, None, None)
     for nb, into in colsum_into.items():
         colsum(dsts[nb][0].view(-1, 64), into, accumulate=True)
     return scales
@@ -1182,7 +1197,7 @@ def patch_dgrad_input_wgrad_ok(k, s, C, Cin):
 PATCH_WGRAD_WEIGHT = os.environ.get('VOXACTB_PATCH_WGRAD_WEIGHT', '1') != '0'      # '0': the patchify weight gradient as its own launch (A/B)
 
 
-def patch_dgrad_input_wgrad(dpatch, Wp, d0, vox, dW, db, B, V, G, k, pad, dWp=None):
+def patch_dgrad_input_wgrad(dpatch, Wp, d0, vox, dW, db, B, V, G, k, pad, dWp=None, act=LRELU):
     """dW [64][10] += / db [64] += the patchify data gradient's share of the input conv's weight / bias gradient, straight from
     dpatch [B, G^3, 64] (patch_wgrad.hip: vxb_patch_dgrad_input_wgrad_f32) -- the 4.7 GB data gradient tensor and its padding
     adjoint are never formed.  dWp (the patchify weight's gradient tensor [64][64][k][k][k], contiguous): += the patchify conv's own
@@ -1197,24 +1212,24 @@ def patch_dgrad_input_wgrad(dpatch, Wp, d0, vox, dW, db, B, V, G, k, pad, dWp=No
     _lib.set_meta('patch_dgrad_input_wgrad[k%d V%d]' % (k, V), 0.0)
     sc = absmax_scale(dpatch)
     _lib.set_meta('patch_dgrad_input_wgrad[k%d V%d]' % (k, V), 2.0 * B * G ** 3 * k ** 3 * 64 * 64 * (2 if dWp is not None else 1))
-    call('vxb_patch_dgrad_input_wgrad_f32', dpatch, wt, d0, vox, B, V, G, k, pad, LRELU_SLOPE, sc, ws, ns, dW, db, dWp, ws_wp)
+    call('vxb_patch_dgrad_input_wgrad_act_f32', dpatch, wt, d0, vox, B, V, G, k, pad, *_act(act), sc, ws, ns, dW, db, dWp, ws_wp)
 
 
 # --------------------------------------------------------------------------------------------- voxel-sized ops
-def pointwise_fwd(x, W, bias):
+def pointwise_fwd(x, W, bias, act=LRELU):
     nvox = x.numel() // x.shape[-1]
     Cout = W.shape[0]
     y = torch.empty(x.shape[:-1] + (Cout,), dtype=torch.float32, device=x.device)
-    call('vxb_pointwise_fwd_f32', x, W, bias, y, nvox, x.shape[-1], Cout, LRELU_SLOPE)
+    call('vxb_pointwise_fwd_act_f32', x, W, bias, y, nvox, x.shape[-1], Cout, *_act(act))
     return y
 
 
-def pointwise_wgrad(x, y, dy, dW, db):
+def pointwise_wgrad(x, y, dy, dW, db, act=LRELU):
     nvox = x.numel() // x.shape[-1]
     Cin = x.shape[-1]
     nb = (nvox + 4095) // 4096
     ws = torch.empty(nb * (64 * Cin + 64), dtype=torch.float32, device=x.device)
-    call('vxb_pointwise_wgrad_f32', x, y, dy, dW, db, ws, nvox, Cin, y.shape[-1], LRELU_SLOPE)
+    call('vxb_pointwise_wgrad_act_f32', x, y, dy, dW, db, ws, nvox, Cin, y.shape[-1], *_act(act))
 
 
 _LIN = {}
@@ -1311,19 +1326,19 @@ def conv3_ss3d_fwd(src0, src1, wt, bias, B, S, act=ACT_LRELU, label=None):
     if FINAL_WINOGRAD and S % 2 == 0:
         wfw, lin = halo_wfrag_wg(wt, C0 + C1), lin_table(S, dev)        # (before the label: their own launches must not take it)
         _lib.set_meta(lbl, flops)
-        call('vxb_conv3_halo_ss3d_wg_bf16x3_f32', src0, src1, C0, C1, B, S, bias, out, act, LRELU_SLOPE, wfw, lin, ws, out_ss, out_max,
+        call('vxb_conv3_halo_ss3d_wg_bf16x3_f32', src0, src1, C0, C1, B, S, bias, out, *_act(act), wfw, lin, ws, out_ss, out_max,
              stats, argmax)
         return out, (out_ss, out_max, stats, argmax)
     wb = to_bf16_nk(wt)
     assert wb.dim() == 3
     wf = halo_wfrag(wb, C0 + C1)
     _lib.set_meta(lbl, flops)
-    call('vxb_conv3_halo_ss3d_bf16x3_f32', src0, src1, C0, C1, B, S, wb, bias, out, act, LRELU_SLOPE, wf, lin_table(S, dev), ws,
+    call('vxb_conv3_halo_ss3d_bf16x3_f32', src0, src1, C0, C1, B, S, wb, bias, out, *_act(act), wf, lin_table(S, dev), ws,
          out_ss, out_max, stats, argmax)
     return out, (out_ss, out_max, stats, argmax)
 
 
-def pointwise_ss3d_fwd(x, W, bias, B, S):
+def pointwise_ss3d_fwd(x, W, bias, B, S, act=LRELU):
     """pointwise_fwd + ss3d_max_fwd of its output in one pass (x [B,S,S,S,Cin] -> y [B,S,S,S,64], (out_ss, out_max, stats, argmax))."""
     dev = x.device
     Cout = W.shape[0]
@@ -1336,18 +1351,18 @@ def pointwise_ss3d_fwd(x, W, bias, B, S):
     out_max = torch.empty((B, Cout), dtype=torch.float32, device=dev)
     stats = torch.empty((B, Cout, 2), dtype=torch.float32, device=dev)
     argmax = torch.empty((B, Cout), dtype=torch.int32, device=dev)
-    call('vxb_pointwise_ss3d_fwd_f32', x, W, bias, y, B, S, x.shape[-1], Cout, LRELU_SLOPE, lin_table(S, dev), ws, out_ss, out_max,
+    call('vxb_pointwise_ss3d_fwd_act_f32', x, W, bias, y, B, S, x.shape[-1], Cout, *_act(act), lin_table(S, dev), ws, out_ss, out_max,
          stats, argmax)
     return y, (out_ss, out_max, stats, argmax)
 
 
-def pointwise_wgrad_ss3d(x, y, dy, dW, db, B, S, stats, out_ss, argmax, g_ss, g_max, fold_src=None, Sp=0, pad=0):
+def pointwise_wgrad_ss3d(x, y, dy, dW, db, B, S, stats, out_ss, argmax, g_ss, g_max, fold_src=None, Sp=0, pad=0, act=LRELU):
     """pointwise_wgrad with the ss3d_max_bwd term of y's pooled features added to dy on the fly (dy itself is not modified);
     fold_src [B, Sp^3, 64]: fold_pad(fold_src, Sp, ..., pad) is added to dy on the fly as well."""
     Cin = x.shape[-1]
     nb = B * ((S ** 3 + 4095) // 4096)
     ws = torch.empty(nb * (64 * Cin + 64), dtype=torch.float32, device=x.device)
-    call('vxb_pointwise_wgrad_ss3d_f32', x, y, dy, dW, db, ws, B, S, Cin, y.shape[-1], LRELU_SLOPE, lin_table(S, x.device), stats,
+    call('vxb_pointwise_wgrad_ss3d_act_f32', x, y, dy, dW, db, ws, B, S, Cin, y.shape[-1], *_act(act), lin_table(S, x.device), stats,
          out_ss, argmax, g_ss, g_max, fold_src, Sp, pad)
 
 
@@ -1371,8 +1386,8 @@ def conv3_c1_fwd(u, w, bias, B, S):
     return q
 
 
-def conv3_c1_dgrad(dq, w, u, du, B, S, accumulate=True, mask=True):
-    call('vxb_conv3_c1_dgrad_f32', dq, w, u, du, B, S, 64, int(accumulate), int(mask), LRELU_SLOPE)
+def conv3_c1_dgrad(dq, w, u, du, B, S, accumulate=True, mask=True, act=LRELU):
+    call('vxb_conv3_c1_dgrad_act_f32', dq, w, u, du, B, S, 64, int(accumulate), int(mask), *_act(act))
     return du
 
 
@@ -1380,13 +1395,13 @@ def c1_dgrad_ss3d_ok(S, C):
     return C == 64 and S % 4 == 0
 
 
-def conv3_c1_dgrad_ss3d(dq, w, u, du, B, S, stats, out_ss, argmax, g_ss, g_max, dbias, accumulate=False, want_scale=False):
+def conv3_c1_dgrad_ss3d(dq, w, u, du, B, S, stats, out_ss, argmax, g_ss, g_max, dbias, accumulate=False, want_scale=False, act=LRELU):
     """du = lrelu'(u) * ([du] + c1 data gradient + the ss3d_max_bwd term of u); dbias += column sums of du.
     want_scale: also return the fp16 operand scale of du ([scale, 1 / scale] on the device, as absmax_scale(du)), taken while du
     is written -- no extra pass over the 4 GB tensor."""
     ws = torch.empty(int(_lib.lib().vxb_conv3_c1_dgrad_ss3d_ws_floats(B, S)), dtype=torch.float32, device=u.device)
     sc = torch.empty(2, dtype=torch.float32, device=u.device) if want_scale else None
-    call('vxb_conv3_c1_dgrad_ss3d_f32', dq, w, u, du, B, S, 64, int(accumulate), LRELU_SLOPE, lin_table(S, u.device), stats, out_ss,
+    call('vxb_conv3_c1_dgrad_ss3d_act_f32', dq, w, u, du, B, S, 64, int(accumulate), *_act(act), lin_table(S, u.device), stats, out_ss,
          argmax, g_ss, g_max, dbias, ws, sc)
     return (du, sc) if want_scale else du
 
@@ -1501,7 +1516,7 @@ def gemm_bf16w(x, Wb, out=None, bias=None, act=ACT_NONE, residual=None, accumula
                 if out is None:
                     out = torch.empty((M_, N_), dtype=torch.float32, device=x.device)
                 _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M_, N_, K_), 2.0 * M_ * N_ * K_)
-                call('vxb_gemm_wide_bf16x3_f16out_f32', x, x.stride(0), wf, out, out.stride(0), bias, residual, M_, N_, K_, act, LRELU_SLOPE, 0,
+                call('vxb_gemm_wide_bf16x3_f16out_f32', x, x.stride(0), wf, out, out.stride(0), bias, residual, M_, N_, K_, *_act(act), 0,
                      f16_out)
                 return out, True
         return gemm_bf16w(x, Wb, out, bias, act, residual, accumulate, label), False
@@ -1517,7 +1532,7 @@ def gemm_bf16w(x, Wb, out=None, bias=None, act=ACT_NONE, residual=None, accumula
         if wf is not None:
             # 128 x 512 workgroup tiles, A read once and three k-tiles ahead, weights as fragments from global memory (gemm_wide.hip)
             _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 2.0 * M * N * K)
-            call('vxb_gemm_wide_bf16x3_f32', x, x.stride(0), wf, out, out.stride(0), bias, residual, M, N, K, act, LRELU_SLOPE,
+            call('vxb_gemm_wide_bf16x3_f32', x, x.stride(0), wf, out, out.stride(0), bias, residual, M, N, K, *_act(act),
                  int(accumulate))
             return out
     # measured at M = 32768 in bf16x3 (tools/bench_gemm.py): N x K = 4096 x 512: 239 TF/s vs 217 (direct-to-LDS 128^2 + weight
@@ -1529,7 +1544,7 @@ def gemm_bf16w(x, Wb, out=None, bias=None, act=ACT_NONE, residual=None, accumula
         _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 0.0)
         planes = split_planes(x, npl)
         _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 2.0 * M * N * K)
-        call('vxb_gemm256_f32', planes, K, Wb, npl, out, out.stride(0), bias, residual, M, N, K, act, LRELU_SLOPE, int(accumulate))
+        call('vxb_gemm256_f32', planes, K, Wb, npl, out, out.stride(0), bias, residual, M, N, K, *_act(act), int(accumulate))
         return out
     _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 2.0 * M * N * K)
     # the split pass costs M*K*(6|8) bytes of HBM traffic; it pays when every A tile is reused by many column tiles
@@ -1541,10 +1556,10 @@ def gemm_bf16w(x, Wb, out=None, bias=None, act=ACT_NONE, residual=None, accumula
         _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 0.0)
         planes = split_planes(x, 2 if x3 else 1)
         _lib.set_meta(label or 'gemm_bf16 %dx%dx%d' % (M, N, K), 2.0 * M * N * K)
-        call('vxb_gemm_dl_f32', planes, Wb, gemm_wfrag(Wb), 2 if x3 else 1, out, out.stride(0), bias, residual, M, N, K, act,
-             LRELU_SLOPE, int(accumulate))
+        call('vxb_gemm_dl_f32', planes, Wb, gemm_wfrag(Wb), 2 if x3 else 1, out, out.stride(0), bias, residual, M, N, K, *_act(act),
+             int(accumulate))
         return out
-    call('vxb_gemm_bf16x3_f32' if x3 else 'vxb_gemm_bf16w_f32', x, x.stride(0), Wb, out, out.stride(0), bias, residual, M, N, K, act, LRELU_SLOPE,
+    call('vxb_gemm_bf16x3_f32' if x3 else 'vxb_gemm_bf16w_f32', x, x.stride(0), Wb, out, out.stride(0), bias, residual, M, N, K, *_act(act),
          int(accumulate))
     return out
 
@@ -1570,7 +1585,7 @@ def conv3d_bf16w(src0, wb, N, B, S_in, S_out, kext, off, stride=1, replicate=Tru
         _lib.set_meta(label or 'conv3d_bf16[k%d s%d %d->%d S%d%s]' % (kext, stride, C0 + C1, N, S_out, '' if replicate else ' dgrad'),
                       2.0 * B * S_out ** 3 * N * kext ** 3 * (C0 + C1))
         call('vxb_conv3_halo_bf16x3_f32' if x3 else 'vxb_conv3_halo_bf16w_f32', src0, src1, C0, C1, B, S_in, S_out, off,
-             int(replicate), wb, N, bias, out, act, LRELU_SLOPE, 0, 0, d2s[0], wf, None, 0, 0)
+             int(replicate), wb, N, bias, out, *_act(act), 0, 0, d2s[0], wf, None, 0, 0)
         return out
     # ... same trade for convs: every input voxel must feed enough products ((kext/stride)^3 * N per channel) to amortise
     # the split pass (up-conv forward 17.7 -> 15.3 ms; the stride-5 patchify would lose 1.5 ms and stays register-staged)
@@ -1582,10 +1597,10 @@ def conv3d_bf16w(src0, wb, N, B, S_in, S_out, kext, off, stride=1, replicate=Tru
         planes = split_planes(src0.view(-1, C0), npl)
         _lib.set_meta(lbl, 2.0 * B * S_out ** 3 * N * kext ** 3 * C0)
         call('vxb_conv3d_dl_f32', planes, C0, B, S_in, S_out, stride, kext, off, int(replicate), wb, gemm_wfrag(wb), npl, N, bias, out,
-             ldc if ldc is not None else N, act, LRELU_SLOPE, int(accumulate), d2s[0], d2s[1], _zeros16(src0.device), None, None)
+             ldc if ldc is not None else N, *_act(act), int(accumulate), d2s[0], d2s[1], _zeros16(src0.device), None, None)
         return out
     call('vxb_conv3d_bf16x3_f32' if x3 else 'vxb_conv3d_bf16w_f32', src0, src1, C0, C1, B, S_in, S_out, stride, kext, off, int(replicate), wb, N, bias, out,
-         ldc if ldc is not None else N, act, LRELU_SLOPE, int(accumulate), d2s[0], d2s[1])
+         ldc if ldc is not None else N, *_act(act), int(accumulate), d2s[0], d2s[1])
     return out
 
 
