@@ -89,8 +89,7 @@ int vxb_voxelize_depth_f32(const float* const* depth_src, const float* const* fe
  *   returns -1 (bad argument).  The backward entries take the activation's SAVED OUTPUT y and multiply the incoming gradient
  *   by the derivative read from it: y > 0 ? 1 : slope for code 1 (PyTorch's ReLU / LeakyReLU backward gate on the output
  *   the same way), 1 - y * y for code 2 (PyTorch's tanh_backward), 1 for code 0.  The fp16 paths that take the operand
- *   scale of a data gradient while writing it (dst_scale, du_scale) take it after this factor.  The backward entries without
- *   `_act` in their name (ABI 4 and earlier) are their *_act_f32 sibling with act = 1. */
+ *   scale of a data gradient while writing it (dst_scale, du_scale) take it after this factor. */
 int vxb_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* residual,
                  int M, int N, int K, int64_t sAm, int64_t sAk, int64_t sBk, int64_t sBn, int64_t ldc,
                  int batch, int H, int64_t bA1, int64_t bA2, int64_t bB1, int64_t bB2, int64_t bC1,
@@ -116,9 +115,7 @@ int vxb_conv3d_wgrad_f32(const float* src0, const float* src1, int C0, int C1, i
                          int stride, int kext, int off, int replicate, const float* dy, int N, int64_t ldy,
                          int d2s_s, int d2s_C, float* part, int nsplit, vxb_stream_t stream);
 /* Adjoint of replicate padding after a data-gradient conv: dst[b,j,c] (+)= sum of src[b,i,c0+c] over the padded
- * positions i that clamp to j; optionally times LeakyReLU'(lrelu_of[b,j,c]) (the producer's activation). */
-int vxb_fold_pad_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
-                     int C, int pad, int accumulate, float slope, vxb_stream_t stream);
+ * positions i that clamp to j; optionally times act'(lrelu_of[b,j,c]) (the producer's activation, code act). */
 int vxb_fold_pad_act_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S, int C,
                          int pad, int accumulate, int act, float slope, vxb_stream_t stream);
 /* Rigid transform of a channels-first point cloud [B, 3, n] (apply_se3_augmentation / perturb_se3,
@@ -321,14 +318,10 @@ int vxb_conv3_halo_ss3d_wg_bf16x3_f32(const float* src0, const float* src1, int 
 /* wfrag (optional, NULL = weights staged through LDS per tap): the same weights pre-shuffled into MFMA fragment order,
  * [N/64][chunk][tap][column tile 2][k half or plane 2][lane 64][8 bf16] with chunk = 32 channels ('bf16') or 16 ('bf16x3');
  * the kernel then loads its B fragments straight from global memory and the 27-tap loop has no barrier.
- * Data gradient of a 3x3x3 replicate-padded conv fused with vxb_fold_pad_f32 (the padded-domain gradient never reaches
+ * Data gradient of a 3x3x3 replicate-padded conv fused with vxb_fold_pad_act_f32 (the padded-domain gradient never reaches
  * HBM): dy [B, S^3, C0]; wt_bf16 = data-gradient weights [N][27*C0] (x3 != 0: planes [2][N][K]); for each 64-column block
- * nb of the N <= 128 columns: dst_nb [B, S^3, 64] (+)= fold(...) (* LeakyReLU'(y_nb) when y_nb != NULL).
+ * nb of the N <= 128 columns: dst_nb [B, S^3, 64] (+)= fold(...) (* act'(y_nb) when y_nb != NULL).
  * Replaces the pair at perceiver_lang_io.py:462 (backward of `final` into d0 and u0). */
-int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
-                             float* dst1, const float* y0, const float* y1, int acc0, int acc1, float slope,
-                             const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
-                             vxb_stream_t stream);
 int vxb_conv3_dgrad_fold_act_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
                                  float* dst1, const float* y0, const float* y1, int acc0, int acc1, int act, float slope,
                                  const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
@@ -339,40 +332,28 @@ size_t vxb_conv3_dgrad_fold_blocks(int B, int S, int N);
 /* ... one 64-column block of it with a single fp16 product per term (dy * scale[0] -> half, result * scale[1]; scale on the
  * device, vxb_absmax_scale_f32; weights in fragment order of the fp16 [64][27 C0] matrix): the d(d0) half of `final`'s data
  * gradient, which only feeds the weight gradient of the 1x1x1 input conv (a leaf of the backward pass). */
-int vxb_conv3_dgrad_fold_f16_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
-                                 int acc, float slope, const float* scale, vxb_stream_t stream);
 int vxb_conv3_dgrad_fold_f16_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
                                      int acc, int act, float slope, const float* scale, vxb_stream_t stream);
-/* ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_dgrad_fold_f16x2_wg_f32): wfrag_f16_wg = ops.halo_wfrag_x2_wg; S even,
+/* ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_dgrad_fold_f16x2_wg_act_f32): wfrag_f16_wg = ops.halo_wfrag_x2_wg; S even,
  * scale required. */
-int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
-                                 int acc, float slope, const float* scale, vxb_stream_t stream);
 int vxb_conv3_dgrad_fold_f16_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst,
                                         const float* y, int acc, int act, float slope, const float* scale, vxb_stream_t stream);
 /* ... on TWO fp16 products per term for a block that propagates (the d(u0) half): dy * scale[0] as an fp16 hi + lo pair, the weights
  * as one fp16 value (wfrag_f16x2: single-plane fragment order of the fp16 [64][27 C0] matrix); optional by-products as in
- * vxb_conv3_dgrad_fold_f32 (dst_scale [2] + scale_ws, dst_colsum [64] ACCUMULATED + colsum_ws). */
-int vxb_conv3_dgrad_fold_f16x2_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
-                                   int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
-                                   float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
+ * vxb_conv3_dgrad_fold_act_f32 (dst_scale [2] + scale_ws, dst_colsum [64] ACCUMULATED + colsum_ws). */
 int vxb_conv3_dgrad_fold_f16x2_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst,
                                        const float* y, int acc, int act, float slope, const float* scale, float* dst_scale,
                                        float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
 /* ... with the filter's depth axis by Winograd's F(2, 3) (see vxb_conv3_halo_ss3d_wg_bf16x3_f32): wfrag_f16x2_wg = ops.halo_wfrag_x2_wg,
  * the 36 transformed taps rounded to fp16 after the transform; S even.  dy * scale[0] / 2 is carried (the transformed operand is a sum
  * of two values).  Against the direct entry: ~1e-6 of the largest output (tests/test_halo_winograd_gpu.py). */
-int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst, const float* y,
-                                   int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
-                                   float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
 int vxb_conv3_dgrad_fold_f16x2_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
                                           const float* y, int acc, int act, float slope, const float* scale, float* dst_scale,
                                           float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream);
 /* ... when that block is the data gradient of a 1x1x1 conv's output y = lrelu(W_in x + b_in) whose input x [B, S^3, 10] is a detached
  * tensor (the input conv of the Q-function, perceiver_lang_io.py:357; agent :100): it only feeds dW_in [64][10] / db_in [64], so it is
- * not stored -- the epilogue multiplies it with LeakyReLU'(y) and x, and the sums are ACCUMULATED into dW / db.
+ * not stored -- the epilogue multiplies it with act'(y) and x, and the sums are ACCUMULATED into dW / db.
  * ws: 704 * (vxb_conv3_dgrad_fold_blocks(B, S, 64) + 512) floats. */
-int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y, const float* x,
-                                      float slope, const float* scale, float* ws, float* dW, float* db, vxb_stream_t stream);
 int vxb_conv3_dgrad_fold_f16_wgin_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
                                           const float* x, int act, float slope, const float* scale, float* ws, float* dW,
                                           float* db, vxb_stream_t stream);
@@ -419,22 +400,16 @@ int vxb_polyphase_weights_f32(const float* W, const float* L, float* Weff, int C
 int vxb_polyphase_weights_bwd_f32(const float* dWeff, const float* L, float* dW, int Cin, int Cout, int k, int s, int kl,
                                   vxb_stream_t stream);
 
-/* 1x1x1 input conv 10 -> 64 + LeakyReLU (perceiver_lang_io.py:357) and its parameter gradients (ACCUMULATED). */
-int vxb_pointwise_fwd_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
-                          int Cout, float slope, vxb_stream_t stream);
+/* 1x1x1 input conv 10 -> 64 + activation act (perceiver_lang_io.py:357) and its parameter gradients (ACCUMULATED). */
 int vxb_pointwise_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin, int Cout,
                               int act, float slope, vxb_stream_t stream);
-int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
-                            int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream);
 int vxb_pointwise_wgrad_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
                                 int64_t nvox, int Cin, int Cout, int act, float slope, vxb_stream_t stream);
 
 /* 3x3x3 conv with one output channel = trans_decoder (perceiver_lang_io.py:465): forward, data gradient
- * (replicate adjoint folded in, optional LeakyReLU' of the producer), parameter gradients (ACCUMULATED). */
+ * (replicate adjoint folded in, optional act' of the producer), parameter gradients (ACCUMULATED). */
 int vxb_conv3_c1_fwd_f32(const float* u, const float* w, const float* bias, float* q, int B, int S, int C,
                          vxb_stream_t stream);
-int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                           int accumulate, int apply_lrelu_mask, float slope, vxb_stream_t stream);
 int vxb_conv3_c1_dgrad_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C, int accumulate,
                                int apply_lrelu_mask, int act, float slope, vxb_stream_t stream);
 int vxb_conv3_c1_wgrad_f32(const float* u, const float* dq, float* dw, float* db, float* part_ws, int B, int S, int C,
@@ -457,35 +432,24 @@ size_t vxb_conv3_c1_wgrad_mfma_blocks(int B, int S);
 
 /* The same two layers fused with the statistics / backward of the pooled features of THEIR OUTPUT (perceiver_lang_io.py:357
  * + :360, network_utils.py:773-809): the forward stores y and folds it into the SpatialSoftmax3D / max partials while it is in
- * registers (bit-identical to vxb_pointwise_fwd_f32 + vxb_ss3d_max_fwd_f32, one pass less over 256 B per voxel); the
+ * registers (bit-identical to vxb_pointwise_fwd_act_f32 + vxb_ss3d_max_fwd_f32, one pass less over 256 B per voxel); the
  * weight gradient adds the term vxb_ss3d_max_bwd_f32 would have written into dy on the fly, and (fold_src != NULL) the
- * padding adjoint vxb_fold_pad_f32 would have added to dy from a [B, Sp^3, 64] data gradient.  x [B,S,S,S,Cin], y / dy
+ * padding adjoint vxb_fold_pad_act_f32 would have added to dy from a [B, Sp^3, 64] data gradient.  x [B,S,S,S,Cin], y / dy
  * [B,S,S,S,64] (dy may be NULL: only the pooled-feature and fold_src terms, when every conv path into y has added its share of
- * dW / db itself: vxb_conv3_dgrad_fold_f16_wgin_f32, vxb_patch_dgrad_input_wgrad_f32); part_ws as for vxb_ss3d_max_fwd_f32 (C = 64), resp. B * ceil(S^3 / 4096) * (64*Cin + 64) floats. */
-int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
-                               float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
-                               int32_t* argmax, vxb_stream_t stream);
+ * dW / db itself: vxb_conv3_dgrad_fold_f16_wgin_act_f32, vxb_patch_dgrad_input_wgrad_act_f32); part_ws as for vxb_ss3d_max_fwd_f32 (C = 64), resp. B * ceil(S^3 / 4096) * (64*Cin + 64) floats. */
 int vxb_pointwise_ss3d_fwd_act_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin,
                                    int Cout, int act, float slope, const float* lin, float* part_ws, float* out_ss,
                                    float* out_max, float* stats, int32_t* argmax, vxb_stream_t stream);
-int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
-                                 int S, int Cin, int Cout, float slope, const float* lin, const float* stats,
-                                 const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
-                                 const float* fold_src, int Sp, int pad, vxb_stream_t stream);
 int vxb_pointwise_wgrad_ss3d_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
                                      int B, int S, int Cin, int Cout, int act, float slope, const float* lin,
                                      const float* stats, const float* out_ss, const int32_t* argmax, const float* g_ss,
                                      const float* g_max, const float* fold_src, int Sp, int pad, vxb_stream_t stream);
 
-/* Backward of everything that reads u = final(...) (perceiver_lang_io.py:462-470) in one pass over u: du = lrelu'(u) *
- * ([du if accumulate] + data gradient of trans_decoder (Cout = 1 conv, vxb_conv3_c1_dgrad_f32) + the pooled-feature term of
+/* Backward of everything that reads u = final(...) (perceiver_lang_io.py:462-470) in one pass over u: du = act'(u) *
+ * ([du if accumulate] + data gradient of trans_decoder (Cout = 1 conv, vxb_conv3_c1_dgrad_act_f32) + the pooled-feature term of
  * vxb_ss3d_max_bwd_f32 on u), and dbias[64] += column sums of du (the bias gradient of `final`).  Bit-identical du to the
  * separate kernels.  S % 4 == 0, C = 64; part_ws: vxb_conv3_c1_dgrad_ss3d_ws_floats(B, S) floats. */
 size_t vxb_conv3_c1_dgrad_ss3d_ws_floats(int B, int S);
-int vxb_conv3_c1_dgrad_ss3d_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                                int accumulate, float slope, const float* lin, const float* stats, const float* out_ss,
-                                const int32_t* argmax, const float* g_ss, const float* g_max, float* dbias,
-                                float* part_ws, float* du_scale, vxb_stream_t stream);
 int vxb_conv3_c1_dgrad_ss3d_act_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
                                     int accumulate, int act, float slope, const float* lin, const float* stats,
                                     const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
@@ -504,18 +468,15 @@ int vxb_ss3d_max_bwd_f32(const float* x, int64_t bs, int B, int S, int C, const 
 /* The patchify data gradient folded into the input conv's weight gradient (perceiver_lang_io.py:357-371: patchify = Conv3DBlock(64 -> 64,
  * k = stride, replicate padding) on d0 = input_preprocess(voxel grid); the grid is a detached input, agent :100, so d(d0) only feeds
  * dW_in / db_in): for every (patch p, tap t), v = clamp(k p + t - pad) per axis,
- *   dW[c][j] += lrelu'(d0[v][c]) * (sum_kout dpatch[p][kout] * Wp[kout][c][t]) * vox[v][j],   db[c] += the same without vox,
+ *   dW[c][j] += act'(d0[v][c]) * (sum_kout dpatch[p][kout] * Wp[kout][c][t]) * vox[v][j],   db[c] += the same without vox,
  * i.e. the padding adjoint and the data gradient tensor (4.7 GB at configs[1]) never exist.  Single fp16 products (a leaf): dpatch is
  * multiplied by scale[0] (device, power of two: vxb_absmax_scale_f32), the sums by scale[1].  wt_f16: fp16 [k^3][64][64] =
  * Wp[kout][c][t] transposed per tap (t = (kd k + kh) k + kw).  dW [64][10], db [64] ACCUMULATED; ws: ..._ws_floats(k, nsplit) floats.
  * dWp (optional; with ws_wp of vxb_patch_wgrad_weight_ws_floats(k, nsplit) floats, both or neither): the patchify conv's own WEIGHT
  * gradient (network_utils.py:128-170 backward), dWp[kout][c][t] += sum_p d0[v(p, t)][c] * dpatch[p][kout] in the parameter's layout --
- * from the d0 values the same launch fetches for lrelu', instead of a second pass over d0. */
+ * from the d0 values the same launch fetches for act', instead of a second pass over d0. */
 size_t vxb_patch_dgrad_input_wgrad_ws_floats(int k, int nsplit);
 size_t vxb_patch_wgrad_weight_ws_floats(int k, int nsplit);
-int vxb_patch_dgrad_input_wgrad_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V, int G,
-                                    int k, int pad, float slope, const float* scale, float* ws, int nsplit, float* dW, float* db,
-                                    float* dWp, float* ws_wp, vxb_stream_t stream);
 int vxb_patch_dgrad_input_wgrad_act_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B,
                                         int V, int G, int k, int pad, int act, float slope, const float* scale, float* ws,
                                         int nsplit, float* dW, float* db, float* dWp, float* ws_wp, vxb_stream_t stream);
@@ -608,10 +569,9 @@ int vxb_flash_attn_bwd_dl(const float* q, const float* kv, const float* o, const
                           float* dkv, float* dsum_ws, int B, int H, int Nq, int Nk, int head_dim, float scale,
                           float dropout_p, uint32_t seed, vxb_stream_t stream);
 
-/* GEGLU x * gelu_erf(gates) (perceiver_lang_io.py:74-77); LeakyReLU backward; y += alpha*x. */
+/* GEGLU x * gelu_erf(gates) (perceiver_lang_io.py:74-77); activation backward; y += alpha*x. */
 int vxb_geglu_fwd_f32(const float* h, float* out, int64_t rows, int F, vxb_stream_t stream);
 int vxb_geglu_bwd_f32(const float* h, const float* dout, float* dh, int64_t rows, int F, vxb_stream_t stream);
-int vxb_lrelu_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, float slope, vxb_stream_t stream);
 int vxb_lrelu_bwd_act_f32(const float* dy, const float* y, float* dx, int64_t n, int act, float slope, vxb_stream_t stream);
 int vxb_axpy_f32(float* dst, const float* src, int64_t n, float alpha, vxb_stream_t stream);
 

@@ -1,5 +1,5 @@
-"""GPU: data gradient of a 3x3x3 replicate-padded conv fused with the adjoint of its padding (vxb_conv3_dgrad_fold_f32)
-against the two-kernel path (zero-padded conv on the padded domain + vxb_fold_pad_f32) and against autograd of the
+"""GPU: data gradient of a 3x3x3 replicate-padded conv fused with the adjoint of its padding (vxb_conv3_dgrad_fold_act_f32)
+against the two-kernel path (zero-padded conv on the padded domain + vxb_fold_pad_act_f32) and against autograd of the
 PyTorch conv (float64) in bf16x3."""
 import pytest
 import torch
@@ -126,7 +126,7 @@ def test_fused_operand_scales_equal_the_absmax_pass():
 
 @pytest.mark.parametrize('B,S,gain', [(2, 18, 1.0), (1, 22, 1e-6), (1, 100, 1.0), (2, 38, 1.0)])
 def test_leaf_block_folded_into_the_input_weight_gradient(B, S, gain):
-    """vxb_conv3_dgrad_fold_f16_wgin_f32: the d(d0) block of `final`'s data gradient is not stored -- its epilogue multiplies it with
+    """vxb_conv3_dgrad_fold_f16_wgin_act_f32: the d(d0) block of `final`'s data gradient is not stored -- its epilogue multiplies it with
     LeakyReLU'(d0) and the voxel inputs and accumulates dW_in [64][10] / db_in [64]: against the stored-tensor route (same fp16
     kernel, then the products in float64)."""
     from .test_ops_gpu import rnd, cl, DEV

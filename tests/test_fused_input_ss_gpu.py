@@ -1,4 +1,4 @@
-"""The input conv fused with the pooled features of its output (vxb_pointwise_ss3d_fwd_f32, vxb_pointwise_wgrad_ss3d_f32):
+"""The input conv fused with the pooled features of its output (vxb_pointwise_ss3d_fwd_act_f32, vxb_pointwise_wgrad_ss3d_act_f32):
 forward bit-identical to the two-kernel path, gradients against torch autograd of the reference formulation
 (perceiver_lang_io.py:357 + :360; network_utils.py:773-809)."""
 import pytest
@@ -86,7 +86,7 @@ def test_fused_weight_gradient_with_padding_adjoint():
 
 @pytest.mark.parametrize('B,V,gain,wscale', [(2, 10, 1.0, 0.05), (1, 23, 3e-7, 0.05), (3, 12, 2e5, 0.05), (2, 10, 1.0, 1.0), (2, 10, 4e3, 1.0)])
 def test_patchify_data_gradient_folded_into_the_input_weight_gradient(B, V, gain, wscale):
-    """vxb_patch_dgrad_input_wgrad_f32: the patchify block's data gradient (k = stride = 5, replicate padding 2) never becomes a
+    """vxb_patch_dgrad_input_wgrad_act_f32: the patchify block's data gradient (k = stride = 5, replicate padding 2) never becomes a
     tensor -- its share of dW_in [64][10] / db_in [64] straight from dpatch, against torch autograd in float64: the gradient of the
     replicate-padded stride-5 conv w.r.t. d0, times LeakyReLU'(d0), times the voxel inputs.  Ragged grids (V = 23, 12: voxels the
     patches never reach get nothing), tiny / huge gradients (device-side power-of-two scale), accumulation into non-zero dW / db.

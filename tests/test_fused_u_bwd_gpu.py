@@ -1,4 +1,4 @@
-"""vxb_conv3_c1_dgrad_ss3d_f32: the backward of everything that reads u = final(...) in one pass (pooled-feature term of
+"""vxb_conv3_c1_dgrad_ss3d_act_f32: the backward of everything that reads u = final(...) in one pass (pooled-feature term of
 SpatialSoftmax3D + max, translation head's data gradient, LeakyReLU', bias column sums) against the three separate kernels
 (each of which is checked against torch in test_ops_gpu.py / test_c1_conv_gpu.py): du bit-identical, column sums to 1e-5."""
 import pytest

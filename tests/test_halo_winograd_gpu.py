@@ -81,7 +81,7 @@ def test_unsupported_depths_fall_back_to_the_direct_kernel():
 
 @pytest.mark.parametrize('S,B', [(16, 1), (18, 1), (20, 2), (100, 1)])      # S + 2 = 18 / 20 / 22 / 102: two-deep last depth tiles, 6-wide edges
 def test_winograd_data_gradient_against_the_direct_kernel(S, B):
-    """the propagating (fp16x2) half of `final`'s data gradient + padding adjoint (vxb_conv3_dgrad_fold_f16x2_wg_f32) against the direct
+    """the propagating (fp16x2) half of `final`'s data gradient + padding adjoint (vxb_conv3_dgrad_fold_f16x2_wg_act_f32) against the direct
     launch and, for the small grids, a float64 conv_transpose3d folded by the adjoint of the replicate padding."""
     C, N = 64, 128
     dy = cl(rnd(B, C, S, S, S, seed=3)).to(DEV)

@@ -14,21 +14,12 @@
 //             ds_read_b64_tr_b16 into v_mfma_f32_16x16x32_bf16 (k = 32 voxels), exactly like wgrad_halo.hip.
 // Products are bf16x3 (hi*hi + hi*lo + lo*hi, fp32 accumulate) in both precisions: the pass is HBM-bound either way.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-__device__ __forceinline__ void cm_split2(float a, float b, unsigned& ph, unsigned& pl) {
-    ph = vxb_pack_bf16(a, b);
-    pl = vxb_pack_bf16(a - __uint_as_float(ph << 16), b - __uint_as_float(ph & 0xffff0000u));
-}
 
 // ------------------------------------------------------------------------------------------------ forward
 constexpr int FT_D = 4, FT_H = 8, FT_W = 8;            // output tile
@@ -47,7 +38,7 @@ __global__ void __launch_bounds__(256) c1_wfrag_kernel(const float* __restrict__
     for (int e = 0; e < 8; e += 2) {
         const int c = 16 * ks + 8 * half + e;
         const float a = n < 27 ? w[c * 27 + n] : 0.f, b = n < 27 ? w[(c + 1) * 27 + n] : 0.f;
-        cm_split2(a, b, hi[e >> 1], lo[e >> 1]);
+        vxb_split2(a, b, hi[e >> 1], lo[e >> 1]);
     }
     uint4* o = reinterpret_cast<uint4*>(wf);
     o[(ks * 2 + 0) * 64 + lane] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
@@ -103,8 +94,8 @@ __global__ void __launch_bounds__(256, 2) c1_fwd_mfma_kernel(const float* __rest
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 union { unsigned x[4]; bf16x8 v; } ah, al;
-                cm_split2(va[ks].x, va[ks].y, ah.x[0], al.x[0]); cm_split2(va[ks].z, va[ks].w, ah.x[1], al.x[1]);
-                cm_split2(vb[ks].x, vb[ks].y, ah.x[2], al.x[2]); cm_split2(vb[ks].z, vb[ks].w, ah.x[3], al.x[3]);
+                vxb_split2(va[ks].x, va[ks].y, ah.x[0], al.x[0]); vxb_split2(va[ks].z, va[ks].w, ah.x[1], al.x[1]);
+                vxb_split2(vb[ks].x, vb[ks].y, ah.x[2], al.x[2]); vxb_split2(vb[ks].z, vb[ks].w, ah.x[3], al.x[3]);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al.v, bh[ks], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bl[ks], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah.v, bh[ks], acc, 0, 0, 0);
@@ -137,19 +128,11 @@ constexpr int UPL = 128 * ULD, BPL = 128 * BLD;        // u16 per plane
 constexpr int QH_D = GT_D + 2, QH_H = GT_H + 2, QH_W = GT_W + 2;
 constexpr int QNPOS = QH_D * QH_H * QH_W;              // 400 dq halo voxels
 
-__device__ __forceinline__ bf16x8 cm_frag(const u16* p0, const u16* p1) {
-    union { s16x4 s[2]; bf16x8 v; } t;
-    t.s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p0));
-    t.s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p1));
-    return t.v;
-}
-
 // part[blk][c * 27 + t], partB[blk]: partial sums of workgroup blk over its run of voxel tiles (summed by c1_reduce_kernel)
 // F16 = 1 (round 4): ONE fp16 product per term -- this weight gradient is a leaf of the backward pass like the other conv weight
 // gradients -- with dq * scale[0] (a device-side power of two that brings max |dq| into [2^14, 2^15): dq = softmax - onehot
 // spans 1 .. 1e-9) and the sums multiplied by scale[1].  The bf16x3 form spends 24 VALU instructions per MFMA on the hi / lo splits of u
 // and of the 128 x 32 Bq tile (2.6 TB/s for a pass that reads u once); fp16 needs a third of the MFMAs and a quarter of the conversions.
-typedef _Float16 cm_f16x8 __attribute__((ext_vector_type(8)));
 template <int F16>
 __global__ void __launch_bounds__(256, 2) c1_wgrad_mfma_kernel(const float* __restrict__ u, const float* __restrict__ dq,
                                                               float* __restrict__ part, float* __restrict__ partB, int B, int S,
@@ -228,7 +211,7 @@ __global__ void __launch_bounds__(256, 2) c1_wgrad_mfma_kernel(const float* __re
                 hi2.y = vxb_pack_f16(__builtin_amdgcn_fmed3f(pu[i].z, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(pu[i].w, -65504.f, 65504.f));
                 *reinterpret_cast<uint2*>(&us[(e >> 4) * ULD + (e & 15) * 4]) = hi2;
             } else {
-                cm_split2(pu[i].x, pu[i].y, hi2.x, lo2.x); cm_split2(pu[i].z, pu[i].w, hi2.y, lo2.y);
+                vxb_split2(pu[i].x, pu[i].y, hi2.x, lo2.x); vxb_split2(pu[i].z, pu[i].w, hi2.y, lo2.y);
                 *reinterpret_cast<uint2*>(&us[(e >> 4) * ULD + (e & 15) * 4]) = hi2;
                 *reinterpret_cast<uint2*>(&us[UPL + (e >> 4) * ULD + (e & 15) * 4]) = lo2;
             }
@@ -304,19 +287,19 @@ __global__ void __launch_bounds__(256, 2) c1_wgrad_mfma_kernel(const float* __re
             const u16* ua1 = ua0 + GT_W * ULD;
             const u16* bb0 = bs + vox * BLD + fc;
             const u16* bb1 = bb0 + GT_W * BLD;
-            const bf16x8 ah = cm_frag(ua0, ua1);
+            const bf16x8 ah = vxb_frag(ua0, ua1);
             if (F16) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const bf16x8 bh = cm_frag(bb0 + 16 * j, bb1 + 16 * j);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cm_f16x8, ah), __builtin_bit_cast(cm_f16x8, bh), acc[j], 0, 0, 0);
+                    const bf16x8 bh = vxb_frag(bb0 + 16 * j, bb1 + 16 * j);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), acc[j], 0, 0, 0);
                 }
                 continue;
             }
-            const bf16x8 al = cm_frag(ua0 + UPL, ua1 + UPL);
+            const bf16x8 al = vxb_frag(ua0 + UPL, ua1 + UPL);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const bf16x8 bh = cm_frag(bb0 + 16 * j, bb1 + 16 * j), bl = cm_frag(bb0 + BPL + 16 * j, bb1 + BPL + 16 * j);
+                const bf16x8 bh = vxb_frag(bb0 + 16 * j, bb1 + 16 * j), bl = vxb_frag(bb0 + BPL + 16 * j, bb1 + BPL + 16 * j);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[j], 0, 0, 0);

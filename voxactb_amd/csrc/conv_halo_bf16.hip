@@ -19,14 +19,10 @@
 // patch of voxels that forms one 32-row MFMA tile is conflict-free for ds_read_b128 (brute-forced over the four
 // 16-lane service groups of that instruction).  Output: C[row = voxel][col = channel] -> 128-byte stores per voxel.
 #include "common.h"
+#include "device_prims.h"
 #include "ss3d.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int TD = 4, TH = 8, TW = 8;                 // output tile
 constexpr int HDp = TD + 2, HHp = TH + 2, HWp = 12;   // halo extents (w padded 10 -> 12)
@@ -564,16 +560,15 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
                 hv[i] = *reinterpret_cast<const float4*>(src + (vbase + st_goff[i]) * Cs + c0 + (((tid + NTH * i) % F4P) * 4));
         }
     };
-    // BL: this wave's quarter (fragment `wid`) of round r_ of chunk ch_: 1 KB, lane l's 16 bytes to LDS[ring slot + wid KB + 16 l].  Issued as
-    // inline asm: the compiler's counter model does not see it (it would put s_waitcnt vmcnt(0) in front of every LDS read that may alias
-    // the destination); the counted waits are placed by hand (bl_wait).  A visible load's compiler-placed wait only gets stricter by it.
+    // BL: this wave's quarter (fragment `wid`) of round r_ of chunk ch_: 1 KB, lane l's 16 bytes to LDS[ring slot + wid KB + 16 l] through
+    // vxb_load_lds_dwordx4 (device_prims.h: invisible to the compiler's wait counting); the counted waits are placed by hand (bl_wait).
     const int widu = __builtin_amdgcn_readfirstlane(wid);
     auto bl_issue = [&](int ch_, int r_) __attribute__((always_inline)) {
         const unsigned long long sp_ = (unsigned long long)(g.wfrag + (((long long)(n0 / N) * wf_rows + (long long)ch_ * NTAP) * (NTG * NF) + (long long)r_ * 4 + widu) * 512);
         const unsigned slo_ = __builtin_amdgcn_readfirstlane((unsigned)sp_), shi_ = __builtin_amdgcn_readfirstlane((unsigned)(sp_ >> 32));
         const u16* src_ = reinterpret_cast<const u16*>(((unsigned long long)shi_ << 32) | slo_);
         const unsigned ldsb_ = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)(halo + RING_OFF + (r_ % RING_NR) * 2048 + widu * 512));
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"((unsigned)(lane * 16)), "s"(src_), "s"(ldsb_) : "memory", "m0");
+        vxb_load_lds_dwordx4(src_, (unsigned)(lane * 16), ldsb_);
     };
     auto bl_wait = [&](int n_) __attribute__((always_inline)) {
         switch (n_) {          // (n_ is a constant after unrolling)
@@ -874,7 +869,7 @@ __device__ __forceinline__ void conv3_halo_body(const HaloArgs& g) {
             }
     }
     if (g.fold_pad > 0) {
-        // ---- fused adjoint of the replicate padding (vxb_fold_pad_f32 without the round trip through HBM): the tile goes
+        // ---- fused adjoint of the replicate padding (vxb_fold_pad_act_f32 without the round trip through HBM): the tile goes
         // to LDS as fp32 [256 voxels][64 ch] (the halo / weight buffers are free now); the voxel that is the first of the
         // padded voxels clamping to an output voxel sums its (pad+1)-wide border group -- the host checked that every
         // group lies inside one tile -- and updates the destination
@@ -1358,7 +1353,7 @@ extern "C" int vxb_conv3_s2d_splitk_f32(const float* src_fine, int C0, int B, in
 }
 
 // Data gradient of a 3x3x3 replicate-padded conv fused with the adjoint of its padding (vxb_conv3_halo_* followed by
-// vxb_fold_pad_f32, without writing the padded-domain gradient): dy [B, S^3, C0] -> for each 64-column block nb of the
+// vxb_fold_pad_act_f32, without writing the padded-domain gradient): dy [B, S^3, C0] -> for each 64-column block nb of the
 // N <= 128 input channels, dst_nb [B, S^3, 64] (+)= fold(conv_zero_pad(dy, wt_dgrad)) (* the derivative of the producer's activation at y_nb -- act_bwd -- when y_nb is
 // given).  x3 != 0: weights are the [2][N][K] planes ('bf16x3').  pad = 1.
 extern "C" int vxb_conv3_dgrad_fold_act_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
@@ -1425,7 +1420,7 @@ extern "C" int vxb_conv3_dgrad_fold_f16_act_f32(const float* dy, int C0, int B, 
     return dgrad_fold_f16(dy, C0, B, S, wfrag_f16, dst, y, acc, act, slope, scale, stream, 0);
 }
 // ... with the depth axis by Winograd's F(2, 3): wfrag = ops.halo_wfrag_x2_wg (the 36 transformed taps in fp16, 16-channel chunks);
-// S even.  See vxb_conv3_dgrad_fold_f16x2_wg_f32.
+// S even.  See vxb_conv3_dgrad_fold_f16x2_wg_act_f32.
 extern "C" int vxb_conv3_dgrad_fold_f16_wg_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
                                                int acc, int act, float slope, const float* scale, vxb_stream_t stream) {
     if (!vxb_act_ok(act)) return VXB_EARG;
@@ -1436,7 +1431,7 @@ extern "C" int vxb_conv3_dgrad_fold_f16_wg_act_f32(const float* dy, int C0, int 
 // One 64-column block of the data gradient + padding adjoint on TWO fp16 products per term ("fp16x2": dy * scale[0] as an fp16
 // hi + lo pair, the weights as one fp16 value; wfrag_f16x2 = ops.halo_wfrag_x2 of the fp16 [64][27 C0] matrix): for the blocks that
 // PROPAGATE -- the d(u0) half of `final`'s data gradient (perceiver_lang_io.py:462) -- with the optional by-products of
-// vxb_conv3_dgrad_fold_f32 (operand scale of dst, column sums of dst).  Against the reference's gradients the weight rounding of a
+// vxb_conv3_dgrad_fold_act_f32 (operand scale of dst, column sums of dst).  Against the reference's gradients the weight rounding of a
 // data gradient moves no gate (tools/experiments/emu_precision.py --round5), and a third of the MFMAs is gone.
 static int dgrad_fold_f16x2(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
                             int acc, int act, float slope, const float* scale, float* dst_scale, float* scale_ws,
@@ -1482,7 +1477,7 @@ extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_act_f32(const float* dy, int C0, in
 // The same launch when the 64-column block is the data gradient of a 1x1x1 conv's OUTPUT y [B, S^3, 64] = lrelu(W_in x + b_in) whose
 // input x [B, S^3, 10] is a detached tensor (the input conv of the Q-function, perceiver_lang_io.py:357; agent :100): that gradient only
 // feeds dW_in [64][10] / db_in [64], so it is not stored -- the epilogue multiplies it with LeakyReLU'(y) and the voxel's inputs and the
-// sums are ACCUMULATED into dW / db (4.1 GB less written here, 4.1 GB less read by vxb_pointwise_wgrad_ss3d_f32).
+// sums are ACCUMULATED into dW / db (4.1 GB less written here, 4.1 GB less read by vxb_pointwise_wgrad_ss3d_act_f32).
 // ws: 704 * (vxb_conv3_dgrad_fold_blocks(B, S, 64) + 512) floats.
 extern "C" int vxb_conv3_dgrad_fold_f16_wgin_act_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
                                                  const float* x, int act, float slope, const float* scale, float* ws, float* dW, float* db,
@@ -1501,35 +1496,4 @@ extern "C" int vxb_conv3_dgrad_fold_f16_wgin_act_f32(const float* dy, int C0, in
                      wfrag_f16, nullptr, 0, 0, 0, scale);
     if (rc) return rc;
     return vxb_wgin_finish_launch(ws, (int)vxb_conv3_dgrad_fold_blocks(B, S, 64), scale, dW, db, (hipStream_t)stream);
-}
-
-// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
-extern "C" int vxb_conv3_dgrad_fold_f32(const float* dy, int C0, int B, int S, const void* wt_bf16, int x3, int N, float* dst0,
-                                        float* dst1, const float* y0, const float* y1, int acc0, int acc1, float slope,
-                                        const void* wfrag, float* dst_scale, float* scale_ws, float* dst_colsum, float* colsum_ws,
-                                        vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_act_f32(dy, C0, B, S, wt_bf16, x3, N, dst0, dst1, y0, y1, acc0, acc1, VXB_ACT_LRELU, slope, wfrag, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
-}
-extern "C" int vxb_conv3_dgrad_fold_f16_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, float* dst, const float* y,
-                                            int acc, float slope, const float* scale, vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_f16_act_f32(dy, C0, B, S, wfrag_f16, dst, y, acc, VXB_ACT_LRELU, slope, scale, stream);
-}
-extern "C" int vxb_conv3_dgrad_fold_f16_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16_wg, float* dst, const float* y,
-                                               int acc, float slope, const float* scale, vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_f16_wg_act_f32(dy, C0, B, S, wfrag_f16_wg, dst, y, acc, VXB_ACT_LRELU, slope, scale, stream);
-}
-extern "C" int vxb_conv3_dgrad_fold_f16x2_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2, float* dst, const float* y,
-                                              int acc, float slope, const float* scale, float* dst_scale, float* scale_ws,
-                                              float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_f16x2_act_f32(dy, C0, B, S, wfrag_f16x2, dst, y, acc, VXB_ACT_LRELU, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
-}
-extern "C" int vxb_conv3_dgrad_fold_f16x2_wg_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16x2_wg, float* dst,
-                                                 const float* y, int acc, float slope, const float* scale, float* dst_scale,
-                                                 float* scale_ws, float* dst_colsum, float* colsum_ws, vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_f16x2_wg_act_f32(dy, C0, B, S, wfrag_f16x2_wg, dst, y, acc, VXB_ACT_LRELU, slope, scale, dst_scale, scale_ws, dst_colsum, colsum_ws, stream);
-}
-extern "C" int vxb_conv3_dgrad_fold_f16_wgin_f32(const float* dy, int C0, int B, int S, const void* wfrag_f16, const float* y,
-                                                 const float* x, float slope, const float* scale, float* ws, float* dW, float* db,
-                                                 vxb_stream_t stream) {
-    return vxb_conv3_dgrad_fold_f16_wgin_act_f32(dy, C0, B, S, wfrag_f16, y, x, VXB_ACT_LRELU, slope, scale, ws, dW, db, stream);
 }

@@ -16,21 +16,15 @@
 // A preparation pass (f2b_prep_*) makes D = rowsum(dO * O), max|dO|, the 16-bit planes of q and dO' and, per query row, the offset
 // fragment {-lse2 as three 16-bit parts, row-beyond-Nq flag, -2^k D as three parts}.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int HD = 64, BT = 64;
 constexpr int TILE = BT * HD;               // u16 per plane tile (8 KB)
 constexpr int NST = 4;
 constexpr float LOG2E = 1.4426950408889634f;
-
-enum { M_BF16 = 0, M_F16 = 1 };
 
 struct F2bArgs {
     const float* q;        // [B, Nq, H*64] fp32
@@ -52,71 +46,21 @@ struct F2bArgs {
     unsigned seed;
 };
 
-__device__ __forceinline__ unsigned fb_hash(unsigned x) {      // == f2_hash: the forward's dropout mask
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return x;
-}
-template <int MODE>
-__device__ __forceinline__ unsigned fb_pack(float a, float b) {
-    return MODE == M_BF16 ? vxb_pack_bf16(a, b) : vxb_pack_f16(a, b);
-}
-template <int MODE>
-__device__ __forceinline__ void fb_unpack(unsigned p, float& a, float& b) {
-    if (MODE == M_BF16) { a = __uint_as_float(p << 16); b = __uint_as_float(p & 0xffff0000u); }
-    else {
-        union { unsigned u; vxb_f16x2 h; } t; t.u = p;
-        a = (float)t.h[0]; b = (float)t.h[1];
-    }
-}
 template <int MODE>
 __device__ __forceinline__ float fb_clamp(float x) { return MODE == M_BF16 ? x : __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
-template <int MODE>
-__device__ __forceinline__ f32x16 fb_mma(const bf16x8 a, const bf16x8 b, f32x16 c) {
-    if (MODE == M_BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 fb_from4(unsigned a, unsigned b, unsigned c, unsigned d) {
-    union { unsigned u[4]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b; t.u[2] = c; t.u[3] = d;
-    return t.v;
-}
-__device__ __forceinline__ bf16x8 fb_join(unsigned long long a, unsigned long long b) {
-    union { unsigned long long u[2]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b;
-    return t.v;
-}
-typedef short fb_v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned long long fb_tr16(const u16* p) {
-    union { fb_v4s v; unsigned long long u; } t;
-    t.v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fb_v4s*)p);
-    return t.u;
-}
-// direct-to-LDS loads as inline asm (see flash2_fwd.hip: the compiler must not know about them); 16 or 4 bytes per lane
-__device__ __forceinline__ void fb_load16(const void* base, unsigned byte_off, unsigned lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(byte_off), "s"(base), "s"(lds_wave_base) : "memory");
-}
-__device__ __forceinline__ void fb_load4(const void* base, unsigned byte_off, unsigned lds_wave_base) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(byte_off), "s"(base), "s"(lds_wave_base) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void fb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ int fb_swz(int row) {           // chunk XOR key of a tile row: conflict-free for ds_read_b128 AND transposed reads
-    const int x = (row >> 1) & 7;
-    return ((x & 1) << 2) | (x >> 1);
-}
 // x as three 16-bit parts (hi + mid + lo == x to 2^-33 |x| in fp16, 2^-24 in bf16)
 template <int MODE>
 __device__ __forceinline__ void fb_split3(float x, unsigned& w01, unsigned& w2) {
     x = fb_clamp<MODE>(x);
-    const unsigned ph = fb_pack<MODE>(x, 0.f);
+    const unsigned ph = vxb_pack<MODE>(x, 0.f);
     float h, z;
-    fb_unpack<MODE>(ph, h, z);
+    vxb_unpack<MODE>(ph, h, z);
     const float r1 = x - h;
-    const unsigned pm = fb_pack<MODE>(r1, 0.f);
+    const unsigned pm = vxb_pack<MODE>(r1, 0.f);
     float m;
-    fb_unpack<MODE>(pm, m, z);
+    vxb_unpack<MODE>(pm, m, z);
     w01 = (ph & 0xffffu) | (pm << 16);
-    w2 = fb_pack<MODE>(r1 - m, 0.f) & 0xffffu;
+    w2 = vxb_pack<MODE>(r1 - m, 0.f) & 0xffffu;
 }
 
 // DROP == 2: the forward's keep words (flash2_fwd.hip: f2_store_keep) instead of the hash.  Both kernels take them through LDS with their
@@ -182,18 +126,18 @@ __global__ void __launch_bounds__(256) f2b_prep2_kernel(const float* __restrict_
     if (gid < nvec) {
         const float4 a = *reinterpret_cast<const float4*>(q + gid * 4);
         uint2 w;
-        w.x = fb_pack<MODE>(fb_clamp<MODE>(a.x), fb_clamp<MODE>(a.y)); w.y = fb_pack<MODE>(fb_clamp<MODE>(a.z), fb_clamp<MODE>(a.w));
+        w.x = vxb_pack<MODE>(fb_clamp<MODE>(a.x), fb_clamp<MODE>(a.y)); w.y = vxb_pack<MODE>(fb_clamp<MODE>(a.z), fb_clamp<MODE>(a.w));
         *reinterpret_cast<uint2*>(qp + gid * 4) = w;
         const float4 d = *reinterpret_cast<const float4*>(d_o + gid * 4);
         const float x0 = d.x * c1, x1 = d.y * c1, x2 = d.z * c1, x3 = d.w * c1;
         uint2 hw;
-        hw.x = fb_pack<MODE>(x0, x1); hw.y = fb_pack<MODE>(x2, x3);
+        hw.x = vxb_pack<MODE>(x0, x1); hw.y = vxb_pack<MODE>(x2, x3);
         *reinterpret_cast<uint2*>(dop + gid * 4) = hw;
         if (GX) {
             float h0, h1, h2, h3;
-            fb_unpack<MODE>(hw.x, h0, h1); fb_unpack<MODE>(hw.y, h2, h3);
+            vxb_unpack<MODE>(hw.x, h0, h1); vxb_unpack<MODE>(hw.y, h2, h3);
             uint2 lw;
-            lw.x = fb_pack<MODE>(x0 - h0, x1 - h1); lw.y = fb_pack<MODE>(x2 - h2, x3 - h3);
+            lw.x = vxb_pack<MODE>(x0 - h0, x1 - h1); lw.y = vxb_pack<MODE>(x2 - h2, x3 - h3);
             *reinterpret_cast<uint2*>(dop + do_plane + gid * 4) = lw;
         }
     }
@@ -211,7 +155,7 @@ __global__ void __launch_bounds__(256) f2b_prep2_kernel(const float* __restrict_
             fb_split3<MODE>(nd, d01, d2);
             w = make_uint4(a01, a2, d01, d2);
         } else {
-            w.y = fb_pack<MODE>(0.f, MODE == M_BF16 ? -3.0e38f : -60000.f);
+            w.y = vxb_pack<MODE>(0.f, MODE == M_BF16 ? -3.0e38f : -60000.f);
         }
         *reinterpret_cast<uint4*>(rowslots + gid * 4) = w;
         negd[gid] = nd;
@@ -250,32 +194,32 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
     for (int ks = 0; ks < 4; ++ks) {
         const float4 a = *reinterpret_cast<const float4*>(g.q + qoff + 16 * ks + 8 * hi);
         const float4 c = *reinterpret_cast<const float4*>(g.q + qoff + 16 * ks + 8 * hi + 4);
-        qf[ks] = fb_from4(fb_pack<MODE>(fb_clamp<MODE>(a.x * qs), fb_clamp<MODE>(a.y * qs)), fb_pack<MODE>(fb_clamp<MODE>(a.z * qs), fb_clamp<MODE>(a.w * qs)),
-                          fb_pack<MODE>(fb_clamp<MODE>(c.x * qs), fb_clamp<MODE>(c.y * qs)), fb_pack<MODE>(fb_clamp<MODE>(c.z * qs), fb_clamp<MODE>(c.w * qs)));
+        qf[ks] = vxb_from4(vxb_pack<MODE>(fb_clamp<MODE>(a.x * qs), fb_clamp<MODE>(a.y * qs)), vxb_pack<MODE>(fb_clamp<MODE>(a.z * qs), fb_clamp<MODE>(a.w * qs)),
+                          vxb_pack<MODE>(fb_clamp<MODE>(c.x * qs), fb_clamp<MODE>(c.y * qs)), vxb_pack<MODE>(fb_clamp<MODE>(c.z * qs), fb_clamp<MODE>(c.w * qs)));
         const float4 d0 = *reinterpret_cast<const float4*>(g.d_o + qoff + 16 * ks + 8 * hi);
         const float4 d1 = *reinterpret_cast<const float4*>(g.d_o + qoff + 16 * ks + 8 * hi + 4);
         const float v[8] = {d0.x * c1, d0.y * c1, d0.z * c1, d0.w * c1, d1.x * c1, d1.y * c1, d1.z * c1, d1.w * c1};
         unsigned ph[4], pl[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ph[i] = fb_pack<MODE>(v[2 * i], v[2 * i + 1]);
+            ph[i] = vxb_pack<MODE>(v[2 * i], v[2 * i + 1]);
             if (GX) {
                 float h0, h1;
-                fb_unpack<MODE>(ph[i], h0, h1);
-                pl[i] = fb_pack<MODE>(v[2 * i] - h0, v[2 * i + 1] - h1);
+                vxb_unpack<MODE>(ph[i], h0, h1);
+                pl[i] = vxb_pack<MODE>(v[2 * i] - h0, v[2 * i + 1] - h1);
             }
         }
-        dof[0][ks] = fb_from4(ph[0], ph[1], ph[2], ph[3]);
-        if (GX) dof[NG - 1][ks] = fb_from4(pl[0], pl[1], pl[2], pl[3]);
+        dof[0][ks] = vxb_from4(ph[0], ph[1], ph[2], ph[3]);
+        if (GX) dof[NG - 1][ks] = vxb_from4(pl[0], pl[1], pl[2], pl[3]);
     }
     // offset fragments of this lane's query (hi = 0 lanes), K-side ones
     const long long rsi = (long long)bh * g.Nq64 + min(qrow, g.Nq64 - 1);
     const uint4 rs = *reinterpret_cast<const uint4*>(g.rowslots + rsi * 4);
     const float negd = g.negd[rsi];
-    const unsigned bigw = fb_pack<MODE>(0.f, MODE == M_BF16 ? -3.0e38f : -60000.f) & 0xffff0000u;
-    const bf16x8 slot_s = hi ? fb_from4(0u, 0u, 0u, 0u) : fb_from4(rs.x, (rs.y & 0xffffu) | bigw, 0u, 0u);
-    const bf16x8 slot_t = hi ? fb_from4(0u, 0u, 0u, 0u) : fb_from4(rs.z, rs.w, 0u, 0u);
-    const unsigned one2 = hi ? 0u : fb_pack<MODE>(1.f, 1.f);
+    const unsigned bigw = vxb_pack<MODE>(0.f, MODE == M_BF16 ? -3.0e38f : -60000.f) & 0xffff0000u;
+    const bf16x8 slot_s = hi ? vxb_from4(0u, 0u, 0u, 0u) : vxb_from4(rs.x, (rs.y & 0xffffu) | bigw, 0u, 0u);
+    const bf16x8 slot_t = hi ? vxb_from4(0u, 0u, 0u, 0u) : vxb_from4(rs.z, rs.w, 0u, 0u);
+    const unsigned one2 = hi ? 0u : vxb_pack<MODE>(1.f, 1.f);
 
     f32x16 dqacc[2];
 #pragma unroll
@@ -293,7 +237,7 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
 #pragma unroll
     for (int t = 0; t < LPW; ++t) {
         lkey[t] = (wid + NW * t) * 8 + (lane >> 3);
-        chb[t] = (unsigned)(((lane & 7) ^ fb_swz(lkey[t])) * 16);
+        chb[t] = (unsigned)(((lane & 7) ^ vxb_swz(lkey[t])) * 16);
     }
     // keep words of this wave's 32 rows (DROP == 2): 64 words per key tile, [kb][r][half]
     const unsigned* mwave_g = DROP == 2 ? g.mask + ((size_t)bh * g.nrb + (size_t)(qblk * NW + wid)) * (size_t)g.ntile * 64 : nullptr;
@@ -302,20 +246,20 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
 #pragma unroll
         for (int t = 0; t < LPW; ++t) {
             const unsigned key = (unsigned)min(kt * BT + lkey[t], g.Nk - 1);
-            fb_load16(kbase_g, key * rowb + chb[t], smem0 + (unsigned)(((kt & 3) * TILE + (wid + NW * t) * 512) * 2));
-            fb_load16(vbase_g, key * rowb + chb[t], smem0 + (unsigned)((VOFF + (kt & 3) * TILE + (wid + NW * t) * 512) * 2));
+            vxb_load_lds_dwordx4(kbase_g, key * rowb + chb[t], smem0 + (unsigned)(((kt & 3) * TILE + (wid + NW * t) * 512) * 2));
+            vxb_load_lds_dwordx4(vbase_g, key * rowb + chb[t], smem0 + (unsigned)((VOFF + (kt & 3) * TILE + (wid + NW * t) * 512) * 2));
         }
         // this wave's keep words of the tile: 64 words, lane l -> word l (the words travel through LDS, not by scalar loads: a scalar
         // load's result can only be waited for with lgkmcnt(0), which also drains the LDS fragment reads in flight -- measured: the dQ
         // kernel with scalar-loaded lane masks spent 48.8 % of its time in s_waitcnt and was no faster than hashing the mask)
-        if (DROP == 2) fb_load4(mwave_g, (unsigned)((min(kt, nkt_ - 1) * 64 + lane) * 4), smem0 + (unsigned)((MOFF + ((kt & 3) * NW + wid) * 128) * 2));
+        if (DROP == 2) vxb_load_lds_dword(mwave_g, (unsigned)((min(kt, nkt_ - 1) * 64 + lane) * 4), smem0 + (unsigned)((MOFF + ((kt & 3) * NW + wid) * 128) * 2));
     };
     const unsigned thr = (unsigned)(g.p_drop * 65536.0f);
     const unsigned row_id = (unsigned)bh * (unsigned)g.Nq + (unsigned)qrow;
     const unsigned rowh = row_id * 0x9E3779B1U + g.seed;
     int rbase[2], rkey[2];
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) { const int row = kb * 32 + lq; rbase[kb] = row * 64; rkey[kb] = fb_swz(row); }
+    for (int kb = 0; kb < 2; ++kb) { const int row = kb * 32 + lq; rbase[kb] = row * 64; rkey[kb] = vxb_swz(row); }
     const int t16 = lane & 15, gq = lane >> 4;
     const int trow0 = 4 * (gq >> 1) + (t16 >> 2);
     const int tchunk0 = 2 * (gq & 1) + ((t16 & 3) >> 1), thalf = (t16 & 1) * 4;
@@ -324,7 +268,7 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
     for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ fb_swz(8 * rr + trow0)) * 8 + thalf;
+            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ vxb_swz(8 * rr + trow0)) * 8 + thalf;
 
     const int nkt = (g.Nk + BT - 1) / BT;
 
@@ -333,11 +277,11 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
     };
     auto kt_frag = [&](int kt, int kb, int i) -> bf16x8 {                        // K^T: d block i & 1, keys kb*32 + 16 (i >> 1) .. +16
         const u16* ad = smem + (kt & 3) * TILE + (kb * 32 + 16 * (i >> 1)) * 64;
-        return fb_join(fb_tr16(ad + tlane[i & 1][0]), fb_tr16(ad + tlane[i & 1][1] + 8 * 64));
+        return vxb_join(vxb_tr16(ad + tlane[i & 1][0]), vxb_tr16(ad + tlane[i & 1][1] + 8 * 64));
     };
     auto ones_frag = [&](int kt, int kb) -> bf16x8 {
         const unsigned w1 = (kt * BT + kb * 32 + lq >= g.Nk) ? one2 : one2 & 0xffffu;        // (1, tail)
-        return fb_from4(one2, w1, 0u, 0u);
+        return vxb_from4(one2, w1, 0u, 0u);
     };
     // element pair t = 0..7 of a unit: dS' = exp2(S') * (keep ? T' : -D'), packed hi (| lo)
     auto pair = [&](int colb, const unsigned (&munit)[16], int kb, int t, const f32x16& s, const f32x16& tt, unsigned (&ds)[NG][8]) {
@@ -352,16 +296,16 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
             t1 = __int_as_float((m1 & __float_as_int(t1)) | (~m1 & __float_as_int(negd)));
         } else if (DROP) {
             const unsigned cp = (unsigned)((kb * 32 + (r & 3) + 8 * (r >> 2)) >> 1) * 0x85EBCA77U;
-            const unsigned hsh = fb_hash(rowh ^ ((unsigned)colb + cp));
+            const unsigned hsh = vxb_drop_hash(rowh ^ ((unsigned)colb + cp));
             t0 = (hsh & 0xffffu) >= thr ? t0 : negd;
             t1 = (hsh >> 16) >= thr ? t1 : negd;
         }
         const float s0 = fb_clamp<MODE>(p0 * t0), s1 = fb_clamp<MODE>(p1 * t1);
-        ds[0][t] = fb_pack<MODE>(s0, s1);
+        ds[0][t] = vxb_pack<MODE>(s0, s1);
         if (GX) {
             float h0, h1;
-            fb_unpack<MODE>(ds[0][t], h0, h1);
-            ds[NG - 1][t] = fb_pack<MODE>(s0 - h0, s1 - h1);
+            vxb_unpack<MODE>(ds[0][t], h0, h1);
+            ds[NG - 1][t] = vxb_pack<MODE>(s0 - h0, s1 - h1);
         }
     };
     // One step (pinned issue order).  Unit n = (ktn, kbn): its S' and T' are formed; unit c = (ktc, kbc): its dS from (sc_, tc_);
@@ -387,8 +331,8 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.f;
             const bf16x8 on = ones_frag(ktn, kbn);
-            sn = fb_mma<MODE>(on, slot_s, z);
-            tn = fb_mma<MODE>(on, slot_t, z);
+            sn = vxb_mma<MODE>(on, slot_s, z);
+            tn = vxb_mma<MODE>(on, slot_t, z);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -397,14 +341,14 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
                 const int ks = i >> 1, db = i & 1;
 #pragma unroll
                 for (int p = 0; p < NG; ++p)
-                    dqacc[db] = fb_mma<MODE>(tf[i], fb_from4(dsp[p][4 * ks], dsp[p][4 * ks + 1], dsp[p][4 * ks + 2], dsp[p][4 * ks + 3]), dqacc[db]);
+                    dqacc[db] = vxb_mma<MODE>(tf[i], vxb_from4(dsp[p][4 * ks], dsp[p][4 * ks + 1], dsp[p][4 * ks + 2], dsp[p][4 * ks + 3]), dqacc[db]);
             }
             if (HC) pair(colb, munit, kbc, 2 * i, sc_, tc_, dsc);
             __builtin_amdgcn_sched_barrier(0);
             if (HN) {
-                sn = fb_mma<MODE>(kf[i], qf[i], sn);
+                sn = vxb_mma<MODE>(kf[i], qf[i], sn);
 #pragma unroll
-                for (int p = 0; p < NG; ++p) tn = fb_mma<MODE>(vf[i], dof[p][i], tn);
+                for (int p = 0; p < NG; ++p) tn = vxb_mma<MODE>(vf[i], dof[p][i], tn);
             }
             if (HC) pair(colb, munit, kbc, 2 * i + 1, sc_, tc_, dsc);
             __builtin_amdgcn_sched_barrier(0);
@@ -416,20 +360,20 @@ __global__ void __launch_bounds__(NW * 64, 2) f2b_dq_kernel(F2bArgs g) {
     // ---- units u = 2 kt + kb; step u forms S'T'(u + 1), dS(u), dQ(u - 1).  Prologue = "step -1" and step 0 (tile 0 only);
     //      region j = steps 2j + 1, 2j + 2 (tiles j and j + 1).  Buffers: S'T'(u) in s_[u & 1], dS(u) in dsb[u & 1].
     issue(0); issue(1); issue(2);
-    fb_wait_vm<2 * NLOAD>();
+    vxb_wait_vm<2 * NLOAD>();
     vxb_raw_barrier();
     f32x16 s_[2], t_[2];
     unsigned dsb[2][NG][8];
     step(T_, F_, F_, 0, 0, 0, 0, 0, 0, s_[0], t_[0], s_[0], t_[0], dsb[0], dsb[0]);
     step(T_, T_, F_, 0, 1, 0, 0, 0, 0, s_[1], t_[1], s_[0], t_[0], dsb[0], dsb[0]);
     for (int j = 0; j < nkt; ++j) {
-        fb_wait_vm<NLOAD>();                                // tiles <= j + 1 landed; tile j + 2 may be in flight
+        vxb_wait_vm<NLOAD>();                                // tiles <= j + 1 landed; tile j + 2 may be in flight
         vxb_raw_barrier();
         issue(j + 3);
         step(T_, T_, T_, j + 1, 0, j, 1, j, 0, s_[0], t_[0], s_[1], t_[1], dsb[1], dsb[0]);
         step(T_, T_, T_, j + 1, 1, j + 1, 0, j, 1, s_[1], t_[1], s_[0], t_[0], dsb[0], dsb[1]);
     }
-    fb_wait_vm<0>();
+    vxb_wait_vm<0>();
     if (q_ok) {
         const float f = g.scale * g.scale_ws[1];
         float* op = g.dq + qoff;
@@ -477,15 +421,15 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
     for (int ks = 0; ks < 4; ++ks) {
         const float4 a = *reinterpret_cast<const float4*>(g.kv + koff + 16 * ks + 8 * hi);
         const float4 c = *reinterpret_cast<const float4*>(g.kv + koff + 16 * ks + 8 * hi + 4);
-        kf[ks] = fb_from4(fb_pack<MODE>(fb_clamp<MODE>(a.x * qs), fb_clamp<MODE>(a.y * qs)), fb_pack<MODE>(fb_clamp<MODE>(a.z * qs), fb_clamp<MODE>(a.w * qs)),
-                          fb_pack<MODE>(fb_clamp<MODE>(c.x * qs), fb_clamp<MODE>(c.y * qs)), fb_pack<MODE>(fb_clamp<MODE>(c.z * qs), fb_clamp<MODE>(c.w * qs)));
+        kf[ks] = vxb_from4(vxb_pack<MODE>(fb_clamp<MODE>(a.x * qs), fb_clamp<MODE>(a.y * qs)), vxb_pack<MODE>(fb_clamp<MODE>(a.z * qs), fb_clamp<MODE>(a.w * qs)),
+                          vxb_pack<MODE>(fb_clamp<MODE>(c.x * qs), fb_clamp<MODE>(c.y * qs)), vxb_pack<MODE>(fb_clamp<MODE>(c.z * qs), fb_clamp<MODE>(c.w * qs)));
         const float4 d = *reinterpret_cast<const float4*>(g.kv + koff + inner + 16 * ks + 8 * hi);
         const float4 e = *reinterpret_cast<const float4*>(g.kv + koff + inner + 16 * ks + 8 * hi + 4);
-        vf[ks] = fb_from4(fb_pack<MODE>(fb_clamp<MODE>(d.x), fb_clamp<MODE>(d.y)), fb_pack<MODE>(fb_clamp<MODE>(d.z), fb_clamp<MODE>(d.w)),
-                          fb_pack<MODE>(fb_clamp<MODE>(e.x), fb_clamp<MODE>(e.y)), fb_pack<MODE>(fb_clamp<MODE>(e.z), fb_clamp<MODE>(e.w)));
+        vf[ks] = vxb_from4(vxb_pack<MODE>(fb_clamp<MODE>(d.x), fb_clamp<MODE>(d.y)), vxb_pack<MODE>(fb_clamp<MODE>(d.z), fb_clamp<MODE>(d.w)),
+                          vxb_pack<MODE>(fb_clamp<MODE>(e.x), fb_clamp<MODE>(e.y)), vxb_pack<MODE>(fb_clamp<MODE>(e.z), fb_clamp<MODE>(e.w)));
     }
-    const unsigned one2 = hi ? 0u : fb_pack<MODE>(1.f, 1.f);
-    const bf16x8 ones = fb_from4(one2, one2, 0u, 0u);
+    const unsigned one2 = hi ? 0u : vxb_pack<MODE>(1.f, 1.f);
+    const bf16x8 ones = vxb_from4(one2, one2, 0u, 0u);
     f32x16 dkacc[2], dvacc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -508,7 +452,7 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
 #pragma unroll
     for (int t = 0; t < LPW; ++t) {
         lrow[t] = (wid + NW * t) * 8 + (lane >> 3);
-        chb[t] = (unsigned)(((lane & 7) ^ fb_swz(lrow[t])) * 16);
+        chb[t] = (unsigned)(((lane & 7) ^ vxb_swz(lrow[t])) * 16);
     }
     const int nqt = (g.Nq + BT - 1) / BT;
     auto issue = [&](int qt) {
@@ -516,17 +460,17 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
 #pragma unroll
         for (int t = 0; t < LPW; ++t) {
             const unsigned row = (unsigned)min(qt * BT + lrow[t], g.Nq - 1);
-            fb_load16(qbase_g, row * rowb + chb[t], smem0 + (unsigned)((QOFF + st * TILE + (wid + NW * t) * 512) * 2));
+            vxb_load_lds_dwordx4(qbase_g, row * rowb + chb[t], smem0 + (unsigned)((QOFF + st * TILE + (wid + NW * t) * 512) * 2));
 #pragma unroll
             for (int p = 0; p < NG; ++p)
-                fb_load16(dbase_g, row * rowb + chb[t] + p * planeb, smem0 + (unsigned)((DOFF + (st * NG + p) * TILE + (wid + NW * t) * 512) * 2));
+                vxb_load_lds_dwordx4(dbase_g, row * rowb + chb[t] + p * planeb, smem0 + (unsigned)((DOFF + (st * NG + p) * TILE + (wid + NW * t) * 512) * 2));
         }
         const int qc = min(qt, nqt - 1) * BT;
-        if (wid == 0) fb_load16(rs_g, (unsigned)((qc + lane) * 16), smem0 + (unsigned)((ROFF + st * 512) * 2));
-        if (wid == 1 % NW) fb_load4(nd_g, (unsigned)((qc + lane) * 4), smem0 + (unsigned)((NOFF + st * 128) * 2));
+        if (wid == 0) vxb_load_lds_dwordx4(rs_g, (unsigned)((qc + lane) * 16), smem0 + (unsigned)((ROFF + st * 512) * 2));
+        if (wid == 1 % NW) vxb_load_lds_dword(nd_g, (unsigned)((qc + lane) * 4), smem0 + (unsigned)((NOFF + st * 128) * 2));
         // keep words: row blocks 2 qt, 2 qt + 1 (lanes 0 - 31 | 32 - 63) x the 128 words of this workgroup's two key tiles
         if (DROP == 2 && wid == 2 % NW)
-            fb_load16(mk_g, (unsigned)(((2 * min(qt, nqt - 1) + (lane >> 5)) * g.ntile) * 256 + (lane & 31) * 16), smem0 + (unsigned)((MOFF + st * 512) * 2));
+            vxb_load_lds_dwordx4(mk_g, (unsigned)(((2 * min(qt, nqt - 1) + (lane >> 5)) * g.ntile) * 256 + (lane & 31) * 16), smem0 + (unsigned)((MOFF + st * 512) * 2));
     };
     if (tid < 8) reinterpret_cast<unsigned*>(smem + ZOFF)[tid] = 0u;          // 32 bytes of zeros: the offset fragment of the hi = 1 lanes
 
@@ -535,7 +479,7 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
     const unsigned colc = ((unsigned)key >> 1) * 0x85EBCA77U + 0xC2B2AE3DU;
     int rbase[2], rkey[2];
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) { const int row = qb * 32 + lk; rbase[qb] = row * 64; rkey[qb] = fb_swz(row); }
+    for (int qb = 0; qb < 2; ++qb) { const int row = qb * 32 + lk; rbase[qb] = row * 64; rkey[qb] = vxb_swz(row); }
     const int t16 = lane & 15, gq = lane >> 4;
     const int trow0 = 4 * (gq >> 1) + (t16 >> 2);
     const int tchunk0 = 2 * (gq & 1) + ((t16 & 3) >> 1), thalf = (t16 & 1) * 4;
@@ -544,14 +488,14 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
     for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ fb_swz(8 * rr + trow0)) * 8 + thalf;
+            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ vxb_swz(8 * rr + trow0)) * 8 + thalf;
 
     auto row_frag = [&](int off, int qb, int ks) -> bf16x8 {                       // rows qb*32 + lk of the tile at u16 offset `off`
         return *reinterpret_cast<const bf16x8*>(smem + off + rbase[qb] + (((2 * ks + hi) ^ rkey[qb]) * 8));
     };
     auto tr_frag = [&](int off, int qb, int i) -> bf16x8 {                         // [16 queries qb*32 + 16 (i >> 1) ..][d block i & 1]
         const u16* ad = smem + off + (qb * 32 + 16 * (i >> 1)) * 64;
-        return fb_join(fb_tr16(ad + tlane[i & 1][0]), fb_tr16(ad + tlane[i & 1][1] + 8 * 64));
+        return vxb_join(vxb_tr16(ad + tlane[i & 1][0]), vxb_tr16(ad + tlane[i & 1][1] + 8 * 64));
     };
     // element pair t of unit (qt, qb): rows ql, ql + 1 of this lane's key
     auto pair = [&](int qt, int qb, int mw, int t, const f32x16& s, const f32x16& tt, const float* nd_tile, unsigned (&pp)[8], unsigned (&ds)[NG][8]) {
@@ -571,7 +515,7 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
             const unsigned row0 = (unsigned)bh * (unsigned)g.Nq + (unsigned)(qt * BT + qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi);
             // the mask word of (row, key pair) covers this lane's key and its neighbour's: the even lane hashes row0, the odd lane
             // row0 + 1, and the two swap words (one DPP move) instead of hashing both
-            const unsigned hm = fb_hash(((row0 + kodd) * 0x9E3779B1U + g.seed) ^ colc);
+            const unsigned hm = vxb_drop_hash(((row0 + kodd) * 0x9E3779B1U + g.seed) ^ colc);
             const unsigned ho = (unsigned)__builtin_amdgcn_mov_dpp((int)hm, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
             const unsigned h0 = kodd ? ho : hm, h1 = kodd ? hm : ho;
             const bool k0 = (h0 << hshift) >= thr16, k1 = (h1 << hshift) >= thr16;
@@ -579,13 +523,13 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
             t0 = k0 ? t0 : nd.x; t1 = k1 ? t1 : nd.y;
             pd0 = k0 ? p0 : 0.f; pd1 = k1 ? p1 : 0.f;
         }
-        pp[t] = fb_pack<MODE>(pd0, pd1);
+        pp[t] = vxb_pack<MODE>(pd0, pd1);
         const float s0 = fb_clamp<MODE>(p0 * t0), s1 = fb_clamp<MODE>(p1 * t1);
-        ds[0][t] = fb_pack<MODE>(s0, s1);
+        ds[0][t] = vxb_pack<MODE>(s0, s1);
         if (GX) {
             float h0, h1;
-            fb_unpack<MODE>(ds[0][t], h0, h1);
-            ds[NG - 1][t] = fb_pack<MODE>(s0 - h0, s1 - h1);
+            vxb_unpack<MODE>(ds[0][t], h0, h1);
+            ds[NG - 1][t] = vxb_pack<MODE>(s0 - h0, s1 - h1);
         }
     };
     auto step = [&](auto has_n, auto has_c, auto has_d, int qtn, int qbn, int qtc, int qbc, int qtd, int qbd, f32x16& sn, f32x16& tn,
@@ -615,30 +559,30 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
             f32x16 z;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            sn = fb_mma<MODE>(fb_from4(w.x, w.y, 0u, 0u), ones, z);
-            tn = fb_mma<MODE>(fb_from4(w.z, w.w, 0u, 0u), ones, z);
+            sn = vxb_mma<MODE>(vxb_from4(w.x, w.y, 0u, 0u), ones, z);
+            tn = vxb_mma<MODE>(vxb_from4(w.z, w.w, 0u, 0u), ones, z);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (i + PF < 4) load_group(i + PF);
             if (HD_) {
                 const int ks = i >> 1, db = i & 1;
-                const bf16x8 pf = fb_from4(ppp[4 * ks], ppp[4 * ks + 1], ppp[4 * ks + 2], ppp[4 * ks + 3]);
+                const bf16x8 pf = vxb_from4(ppp[4 * ks], ppp[4 * ks + 1], ppp[4 * ks + 2], ppp[4 * ks + 3]);
 #pragma unroll
-                for (int p = 0; p < NG; ++p) dvacc[db] = fb_mma<MODE>(pf, td[p][i], dvacc[db]);
+                for (int p = 0; p < NG; ++p) dvacc[db] = vxb_mma<MODE>(pf, td[p][i], dvacc[db]);
             }
             if (HC) pair(qtc, qbc, mw, 2 * i, sc_, tc_, nd, ppc, dsc);
             __builtin_amdgcn_sched_barrier(0);
             if (HN) {
-                sn = fb_mma<MODE>(qa[i], kf[i], sn);
+                sn = vxb_mma<MODE>(qa[i], kf[i], sn);
 #pragma unroll
-                for (int p = 0; p < NG; ++p) tn = fb_mma<MODE>(da[p][i], vf[i], tn);
+                for (int p = 0; p < NG; ++p) tn = vxb_mma<MODE>(da[p][i], vf[i], tn);
             }
             if (HD_) {
                 const int ks = i >> 1, db = i & 1;
 #pragma unroll
                 for (int p = 0; p < NG; ++p)
-                    dkacc[db] = fb_mma<MODE>(fb_from4(dsp[p][4 * ks], dsp[p][4 * ks + 1], dsp[p][4 * ks + 2], dsp[p][4 * ks + 3]), tq[i], dkacc[db]);
+                    dkacc[db] = vxb_mma<MODE>(vxb_from4(dsp[p][4 * ks], dsp[p][4 * ks + 1], dsp[p][4 * ks + 2], dsp[p][4 * ks + 3]), tq[i], dkacc[db]);
             }
             if (HC) pair(qtc, qbc, mw, 2 * i + 1, sc_, tc_, nd, ppc, dsc);
             __builtin_amdgcn_sched_barrier(0);
@@ -673,11 +617,11 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
         auto dvdk = [&](int i) {
             if (!HC) return;
             const int ks = i >> 1, db = i & 1;
-            const bf16x8 pf = fb_from4(pp[4 * ks], pp[4 * ks + 1], pp[4 * ks + 2], pp[4 * ks + 3]);
+            const bf16x8 pf = vxb_from4(pp[4 * ks], pp[4 * ks + 1], pp[4 * ks + 2], pp[4 * ks + 3]);
 #pragma unroll
             for (int p = 0; p < NG; ++p) {
-                dvacc[db] = fb_mma<MODE>(pf, td[p][i], dvacc[db]);
-                dkacc[db] = fb_mma<MODE>(fb_from4(ds[p][4 * ks], ds[p][4 * ks + 1], ds[p][4 * ks + 2], ds[p][4 * ks + 3]), tq[i], dkacc[db]);
+                dvacc[db] = vxb_mma<MODE>(pf, td[p][i], dvacc[db]);
+                dkacc[db] = vxb_mma<MODE>(vxb_from4(ds[p][4 * ks], ds[p][4 * ks + 1], ds[p][4 * ks + 2], ds[p][4 * ks + 3]), tq[i], dkacc[db]);
             }
         };
         load_n(0);
@@ -686,8 +630,8 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
             f32x16 z;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            sn = fb_mma<MODE>(fb_from4(w.x, w.y, 0u, 0u), ones, z);
-            tn = fb_mma<MODE>(fb_from4(w.z, w.w, 0u, 0u), ones, z);
+            sn = vxb_mma<MODE>(vxb_from4(w.x, w.y, 0u, 0u), ones, z);
+            tn = vxb_mma<MODE>(vxb_from4(w.z, w.w, 0u, 0u), ones, z);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -697,9 +641,9 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
             if (HC) pair(qtc, qbc, mw, 2 * i, sc_, tc_, nd, pp, ds);
             __builtin_amdgcn_sched_barrier(0);
             if (HN) {
-                sn = fb_mma<MODE>(qa[i], kf[i], sn);
+                sn = vxb_mma<MODE>(qa[i], kf[i], sn);
 #pragma unroll
-                for (int p = 0; p < NG; ++p) tn = fb_mma<MODE>(da[p][i], vf[i], tn);
+                for (int p = 0; p < NG; ++p) tn = vxb_mma<MODE>(da[p][i], vf[i], tn);
             }
             if (i == 2) { dvdk(0); }
             if (i == 3) { dvdk(1); }
@@ -714,7 +658,7 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
 
     if constexpr (!GX) {
         issue(0); issue(1);
-        fb_wait_vm<0>();
+        vxb_wait_vm<0>();
         __syncthreads();
         f32x16 s_[2], t_[2];
         unsigned pp1[8], ds1[NG][8];
@@ -725,7 +669,7 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
         // region j = units (j, 0), (j, 1): tiles j (current, stage j % 3) and j + 1 (the next unit's scores)
         auto region = [&](auto sa, auto sb, int j) {
             step_lean(T_, T_, sa, sa, j, 1, j, 0, s_[1], t_[1], s_[0], t_[0], pp1, ds1);
-            fb_wait_vm<0>();                                // tile j + 1 (requested one region ago) landed
+            vxb_wait_vm<0>();                                // tile j + 1 (requested one region ago) landed
             vxb_raw_barrier();
             if (j + 2 < nqt + 1) issue(j + 2);              // stage (j + 2) % 3 held tile j - 1
             step_lean(T_, T_, sb, sa, j + 1, 0, j, 1, s_[0], t_[0], s_[1], t_[1], pp1, ds1);
@@ -734,23 +678,23 @@ __global__ void __launch_bounds__(NW * 64, GX ? 1 : 2) f2b_dkv_kernel(F2bArgs g)
         for (; j + 3 <= nqt; j += 3) { region(S0(), S1(), j); region(S1(), S2(), j + 1); region(S2(), S0(), j + 2); }
         if (j < nqt) region(S0(), S1(), j);
         if (j + 1 < nqt) region(S1(), S2(), j + 1);
-        fb_wait_vm<0>();
+        vxb_wait_vm<0>();
     } else {
     issue(0); issue(1);
-    fb_wait_vm<0>();
+    vxb_wait_vm<0>();
     __syncthreads();
     f32x16 s_[2], t_[2];
     unsigned ppb[2][8], dsb[2][NG][8];
     step(T_, F_, F_, 0, 0, 0, 0, 0, 0, s_[0], t_[0], s_[0], t_[0], ppb[0], dsb[0], ppb[0], dsb[0]);
     step(T_, T_, F_, 0, 1, 0, 0, 0, 0, s_[1], t_[1], s_[0], t_[0], ppb[0], dsb[0], ppb[0], dsb[0]);
     for (int j = 0; j < nqt; ++j) {
-        fb_wait_vm<0>();                                    // tile j + 1 (requested one region ago) landed
+        vxb_wait_vm<0>();                                    // tile j + 1 (requested one region ago) landed
         vxb_raw_barrier();
         issue(j + 2);                                       // stage (j + 2) % 3 held tile j - 1
         step(T_, T_, T_, j + 1, 0, j, 1, j, 0, s_[0], t_[0], s_[1], t_[1], ppb[1], dsb[1], ppb[0], dsb[0]);
         step(T_, T_, T_, j + 1, 1, j + 1, 0, j, 1, s_[1], t_[1], s_[0], t_[0], ppb[0], dsb[0], ppb[1], dsb[1]);
     }
-    fb_wait_vm<0>();
+    vxb_wait_vm<0>();
     }
     // accumulators: C[i = key (rows, regs)][j = d (lane)]
     const int kw0 = kblk * (NW * 32) + wid * 32;

@@ -28,14 +28,10 @@
 // the probabilities single -- was built and measured first: 1.9x the MFMAs for a 1.4x smaller error, since each product still has
 // one singly-rounded side; dropped.)
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 #ifndef F2_ABLATE
 #define F2_ABLATE 0          // timing experiments only (tools/ab_flash2.sh): 1 no tile loads, 2 no barrier, 4 no exponentials, 8 no LDS fragment reads, 16 no output stores
@@ -50,8 +46,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 #endif
 constexpr float P_LIMIT = F2_PLIMIT;          // a tile's row sum above this -> raise m (every P <= 4096 fits fp16)
 
-enum { M_BF16 = 0, M_F16 = 1 };
-
 struct F2Args {
     const float* q;       // [B, Nq, H*64] fp32
     const u16* kv;        // [B*Nk][2*H*64] bf16 or fp16
@@ -63,54 +57,11 @@ struct F2Args {
     unsigned seed;
 };
 
-__device__ __forceinline__ unsigned f2_hash(unsigned x) {      // == fd_hash (flash_fwd_dl.hip): the backward kernels rebuild the same mask
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return x;
-}
-template <int MODE>
-__device__ __forceinline__ unsigned f2_pack(float a, float b) {
-    return MODE == M_BF16 ? vxb_pack_bf16(a, b) : vxb_pack_f16(a, b);
-}
-// the 16-bit value a pack kept, back as fp32
-template <int MODE>
-__device__ __forceinline__ void f2_unpack(unsigned p, float& a, float& b) {
-    if (MODE == M_BF16) { a = __uint_as_float(p << 16); b = __uint_as_float(p & 0xffff0000u); }
-    else {
-        union { unsigned u; vxb_f16x2 h; } t; t.u = p;
-        a = (float)t.h[0]; b = (float)t.h[1];
-    }
-}
-template <int MODE>
-__device__ __forceinline__ f32x16 f2_mma(const bf16x8 a, const bf16x8 b, f32x16 c) {
-    if (MODE == M_BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 f2_from4(unsigned a, unsigned b, unsigned c, unsigned d) {
-    union { unsigned u[4]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b; t.u[2] = c; t.u[3] = d;
-    return t.v;
-}
-__device__ __forceinline__ bf16x8 f2_join(unsigned long long a, unsigned long long b) {
-    union { unsigned long long u[2]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b;
-    return t.v;
-}
-typedef short f2_v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned long long f2_tr16(const u16* p) {
-    union { f2_v4s v; unsigned long long u; } t;
-    t.v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) f2_v4s*)p);
-    return t.u;
-}
-// 16 bytes per lane, global (base + 32-bit lane offset) -> LDS[wave base + 16 lane], as INLINE ASM: the compiler's waitcnt pass orders
-// every later LDS read behind a direct-to-LDS load it knows about (s_waitcnt vmcnt(0) in front of the first ds_read_b64_tr_b16 of a
-// region -- the loads this kernel keeps in flight on purpose); issued this way it sees nothing and the hand-placed counted waits are
-// the only ones.  m0 = wave base.
+// the K / V tile loads: vxb_load_lds_dwordx4 (device_prims.h: invisible to the compiler's wait counting, waits placed by hand)
 __device__ __forceinline__ void f2_load16(const u16* base, unsigned byte_off, unsigned lds_wave_base) {
     if (F2_ABLATE & 1) return;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(byte_off), "s"(base), "s"(lds_wave_base) : "memory");
+    vxb_load_lds_dwordx4(base, byte_off, lds_wave_base);
 }
-template <int N>
-__device__ __forceinline__ void f2_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // acc += x that the optimiser cannot re-associate: written as plain C the 32 additions of a region's row sum are collected into ONE
 // dependent chain of v_pk_add_f32 behind the last MFMA (16 x (add + s_nop) with nothing to overlap).  The add itself stays a compiler
 // instruction -- as inline asm it would read v_exp_f32's result without the wait state the hazard recogniser inserts (lanes of the
@@ -167,20 +118,20 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
         for (int i = 0; i < 4; ++i) {
             float x0 = v[2 * i], x1 = v[2 * i + 1];
             if (MODE != M_BF16) { x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f); x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f); }
-            ph[i] = f2_pack<MODE>(x0, x1);
+            ph[i] = vxb_pack<MODE>(x0, x1);
         }
-        qf[ks] = f2_from4(ph[0], ph[1], ph[2], ph[3]);
+        qf[ks] = vxb_from4(ph[0], ph[1], ph[2], ph[3]);
     }
     // the fifth k-step: K side (1, 1, tail, 0 ..) in the hi = 0 lanes, query side (-m_hi, -m_lo, -BIG, 0 ..)
-    const unsigned one2 = hi ? 0u : f2_pack<MODE>(1.f, 1.f);
-    const unsigned big2 = hi ? 0u : f2_pack<MODE>(MODE == M_BF16 ? -3.0e38f : -60000.f, 0.f);
+    const unsigned one2 = hi ? 0u : vxb_pack<MODE>(1.f, 1.f);
+    const unsigned big2 = hi ? 0u : vxb_pack<MODE>(MODE == M_BF16 ? -3.0e38f : -60000.f, 0.f);
     unsigned mslot = 0u;                                       // pack(-m_hi, -m_lo)
     float m_run = 0.f, l_run = 0.f;
     auto set_m = [&](float m) {
-        const unsigned ph = f2_pack<MODE>(-m, 0.f);
+        const unsigned ph = vxb_pack<MODE>(-m, 0.f);
         float h0, h1;
-        f2_unpack<MODE>(ph, h0, h1);
-        const unsigned p2 = f2_pack<MODE>(-m, -m - h0);
+        vxb_unpack<MODE>(ph, h0, h1);
+        const unsigned p2 = vxb_pack<MODE>(-m, -m - h0);
         mslot = hi ? 0u : p2;
     };
 
@@ -221,7 +172,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
     const unsigned thr = (unsigned)(g.p_drop * 65536.0f);
     const unsigned row_id = (unsigned)bh * (unsigned)g.Nq + (unsigned)qrow;
     const unsigned rowh = row_id * 0x9E3779B1U + g.seed;
-    unsigned lcg = f2_hash(rowh ^ (hi ? 0x68E31DA4u : 0u));      // DROP == 2: this lane's sequence (the two lanes of a row draw different keys)
+    unsigned lcg = vxb_drop_hash(rowh ^ (hi ? 0x68E31DA4u : 0u));      // DROP == 2: this lane's sequence (the two lanes of a row draw different keys)
     // keep words of this wave's 32 rows: 64 words per key tile (f2_store_keep)
     unsigned* const mwave = DROP == 2 ? g.mask + ((size_t)bh * (size_t)(((g.Nq + 255) >> 8) << 3) + (size_t)(qblk * NW + wid)) * (size_t)((g.Nk + BKV - 1) / BKV) * 64 : nullptr;
     // K fragment (A operand of S^T): key row kb*32 + lq, chunk 2 ks + hi, swizzle key (row >> 1) & 7
@@ -248,11 +199,11 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
         const int kb = gi & 1, i = gi >> 1;
         if (F2_ABLATE & 8) return qf[i ^ 1];
         const u16* ad = smem + VOFF + (kt & 3) * TILE + vlane[(i & 1) ^ kb] + (kb * 32 + 16 * (i >> 1)) * 64;
-        return f2_join(f2_tr16(ad), f2_tr16(ad + 8 * 64));
+        return vxb_join(vxb_tr16(ad), vxb_tr16(ad + 8 * 64));
     };
     auto ones_frag = [&](int kt, int kb) -> bf16x8 {
         const unsigned tail = (kt * BKV + kb * 32 + lq >= g.Nk) ? one2 & 0xffffu : 0u;        // (1, 0): hi = 0 lanes of keys >= Nk
-        return f2_from4(one2, tail, 0u, 0u);
+        return vxb_from4(one2, tail, 0u, 0u);
     };
     // element pair t = 0..15 of tile kts: P = exp2(S') (dropout applied) packed into pc, row-sum contribution into ps[t & 3]
     auto pair = [&](int kts_colb, unsigned* mtile, int t, const f32x16 (&sa)[2], unsigned (&pc)[2][8], float (&ps)[4]) {
@@ -276,11 +227,11 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
             p1 = k1 ? p1 : 0.f;
         } else if (DROP) {
             const unsigned cp = (unsigned)((kb * 32 + (r & 3) + 8 * (r >> 2)) >> 1) * 0x85EBCA77U;
-            const unsigned hsh = f2_hash(rowh ^ ((unsigned)kts_colb + cp));
+            const unsigned hsh = vxb_drop_hash(rowh ^ ((unsigned)kts_colb + cp));
             p0 = (hsh & 0xffffu) >= thr ? p0 : 0.f;
             p1 = (hsh >> 16) >= thr ? p1 : 0.f;
         }
-        pc[kb][r >> 1] = f2_pack<MODE>(p0, p1);
+        pc[kb][r >> 1] = vxb_pack<MODE>(p0, p1);
     };
     // fragments of the NEXT region's first two groups, read at the end of a region (their tiles were waited for at its top)
     bf16x8 kfc[2], vfc[2];
@@ -296,7 +247,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
         constexpr bool HAS_PV = decltype(has_pv)::value;
         const int colb = (int)((unsigned)((kts * BKV + 4 * hi) >> 1) * 0x85EBCA77U + 0xC2B2AE3DU);
         unsigned* const mtile = DROP == 2 ? mwave + (size_t)kts * 64 : nullptr;
-        const bf16x8 msl = f2_from4(mslot, big2, 0u, 0u);
+        const bf16x8 msl = vxb_from4(mslot, big2, 0u, 0u);
         float ps[4] = {0.f, 0.f, 0.f, 0.f};
         bf16x8 kf[10], vf[10];
         kf[0] = kfc[0]; kf[1] = kfc[1]; vf[0] = vfc[0]; vf[1] = vfc[1];
@@ -312,16 +263,16 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
                 f32x16 c;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) c[r] = 0.f;
-                sb[kb] = f2_mma<MODE>(ones_frag(ktq, kb), msl, c);
+                sb[kb] = vxb_mma<MODE>(ones_frag(ktq, kb), msl, c);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (HAS_PV) {
                 const int ks = i >> 1, db = (i & 1) ^ kb;
-                oacc[db] = f2_mma<MODE>(vf[gi], f2_from4(pp[kb][4 * ks], pp[kb][4 * ks + 1], pp[kb][4 * ks + 2], pp[kb][4 * ks + 3]), oacc[db]);
+                oacc[db] = vxb_mma<MODE>(vf[gi], vxb_from4(pp[kb][4 * ks], pp[kb][4 * ks + 1], pp[kb][4 * ks + 2], pp[kb][4 * ks + 3]), oacc[db]);
             }
             pair(colb, mtile, 2 * gi, sa, pc, ps);
             __builtin_amdgcn_sched_barrier(0);
-            sb[kb] = f2_mma<MODE>(kf[gi], qf[i], sb[kb]);
+            sb[kb] = vxb_mma<MODE>(kf[gi], qf[i], sb[kb]);
             pair(colb, mtile, 2 * gi + 1, sa, pc, ps);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -362,20 +313,20 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
     //      Region j consumes K(j+1), V(j-1) and reads the first fragments of K(j+2), V(j): its top waits for {K(j+2), V(j)} and
     //      issues {K(j+4), V(j+2)} -- K slot (j+4) & 3 held K(j) (read in region j-1), V slot (j+2) & 3 held V(j-2) (likewise).
     issue_kv(0, -1); issue_kv(1, -1); issue_kv(2, 0); issue_kv(3, 1);
-    f2_wait_vm<2 * NLOAD>();                               // K0 K1 landed (this wave's part)
+    vxb_wait_vm<2 * NLOAD>();                               // K0 K1 landed (this wave's part)
     vxb_raw_barrier();
     f32x16 sa[2], sb2[2];
     unsigned pa[2][8], pb[2][8];
     {
-        const bf16x8 msl0 = f2_from4(0u, big2, 0u, 0u);
+        const bf16x8 msl0 = vxb_from4(0u, big2, 0u, 0u);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 c;
 #pragma unroll
             for (int r = 0; r < 16; ++r) c[r] = 0.f;
-            c = f2_mma<MODE>(ones_frag(0, kb), msl0, c);
+            c = vxb_mma<MODE>(ones_frag(0, kb), msl0, c);
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) c = f2_mma<MODE>(k_frag(0, 2 * ks + kb), qf[ks], c);
+            for (int ks = 0; ks < 4; ++ks) c = vxb_mma<MODE>(k_frag(0, 2 * ks + kb), qf[ks], c);
             sa[kb] = c;
         }
         float mt = sa[0][0];
@@ -394,7 +345,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
         vfc[0] = kfc[0]; vfc[1] = kfc[1];                  // (region 0 has no P V product)
     }
     // ---- region 0: S'(1) | P(0)
-    f2_wait_vm<NLOAD>();                                   // {K2 V0} landed
+    vxb_wait_vm<NLOAD>();                                   // {K2 V0} landed
     vxb_raw_barrier();
     issue_kv(4, 2);
     {
@@ -407,7 +358,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
     // ---- regions 1 .. nkt-1: S'(j+1) | P(j) | O += V(j-1) P(j-1); P alternates between pa and pb
     int j = 1;
     for (; j + 1 < nkt; j += 2) {
-        f2_wait_vm<NLOAD>();                               // {K(j+2), V(j)} landed (needed by the NEXT region); {K(j+3), V(j+1)} may be in flight
+        vxb_wait_vm<NLOAD>();                               // {K(j+2), V(j)} landed (needed by the NEXT region); {K(j+3), V(j+1)} may be in flight
         vxb_raw_barrier();
         issue_kv(j + 4, j + 2);
         {
@@ -417,7 +368,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) sa[kb] = sb2[kb];
         }
-        f2_wait_vm<NLOAD>();
+        vxb_wait_vm<NLOAD>();
         vxb_raw_barrier();
         issue_kv(j + 5, j + 3);
         {
@@ -438,11 +389,11 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
 #pragma unroll
         for (int gi = 0; gi < 8; ++gi) {
             const int kb = gi & 1, i = gi >> 1, ks = i >> 1, db = (i & 1) ^ kb;
-            oacc[db] = f2_mma<MODE>(vf[gi], f2_from4(pl[kb][4 * ks], pl[kb][4 * ks + 1], pl[kb][4 * ks + 2], pl[kb][4 * ks + 3]), oacc[db]);
+            oacc[db] = vxb_mma<MODE>(vf[gi], vxb_from4(pl[kb][4 * ks], pl[kb][4 * ks + 1], pl[kb][4 * ks + 2], pl[kb][4 * ks + 3]), oacc[db]);
         }
     };
     if (j < nkt) {                                          // one region left: P(j) into pb
-        f2_wait_vm<NLOAD>();
+        vxb_wait_vm<NLOAD>();
         vxb_raw_barrier();
         issue_kv(j + 4, j + 2);
         float ps = region(std::true_type(), j + 1, j, j - 1, sa, sb2, pa, pb);
@@ -452,7 +403,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_kernel(F2Args g) {
     } else {
         last_pv(pa);
     }
-    f2_wait_vm<0>();                                        // the clamped loads of tiles >= nkt must not outlive the workgroup's LDS
+    vxb_wait_vm<0>();                                        // the clamped loads of tiles >= nkt must not outlive the workgroup's LDS
     if (DROP == 2) asm volatile("s_dcache_wb");             // the scalar stores of the keep words leave the scalar data cache
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -525,8 +476,8 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
             ph[i] = vxb_pack_bf16(v[2 * i], v[2 * i + 1]);
             pl[i] = vxb_pack_bf16(v[2 * i] - __uint_as_float(ph[i] << 16), v[2 * i + 1] - __uint_as_float(ph[i] & 0xffff0000u));
         }
-        qfh[ks] = f2_from4(ph[0], ph[1], ph[2], ph[3]);
-        qfl[ks] = f2_from4(pl[0], pl[1], pl[2], pl[3]);
+        qfh[ks] = vxb_from4(ph[0], ph[1], ph[2], ph[3]);
+        qfl[ks] = vxb_from4(pl[0], pl[1], pl[2], pl[3]);
     }
     const unsigned one2 = hi ? 0u : vxb_pack_bf16(1.f, 1.f);
     const unsigned big2 = hi ? 0u : vxb_pack_bf16(-3.0e38f, 0.f);
@@ -592,11 +543,11 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
     };
     auto v_frag = [&](int kt, int kb, int i, int p) -> bf16x8 {             // V^T: d block i & 1, keys kb*32 + 16 (i >> 1) .. +16
         const u16* ad = smem + VOF + ((kt % NS) * 2 + p) * TILE + vlane[i & 1] + (kb * 32 + 16 * (i >> 1)) * 64;
-        return f2_join(f2_tr16(ad), f2_tr16(ad + 8 * 64));
+        return vxb_join(vxb_tr16(ad), vxb_tr16(ad + 8 * 64));
     };
     auto ones_frag = [&](int kt, int kb) -> bf16x8 {
         const unsigned tail = (kt * BKV + kb * 32 + lq >= g.Nk) ? one2 & 0xffffu : 0u;
-        return f2_from4(one2, tail, 0u, 0u);
+        return vxb_from4(one2, tail, 0u, 0u);
     };
     // element pair t = 0..7 of unit (kt, kb): P = exp2(S') (dropout applied) as hi | lo pairs, row-sum contributions
     auto pair = [&](int colb, int kb, int t, const f32x16& s, unsigned (&pc)[2][8], float (&ps)[4]) {
@@ -606,7 +557,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
         f2_acc(ps[(t + 2) & 3], p1);
         if (DROP) {
             const unsigned cp = (unsigned)((kb * 32 + (r & 3) + 8 * (r >> 2)) >> 1) * 0x85EBCA77U;
-            const unsigned hsh = f2_hash(rowh ^ ((unsigned)colb + cp));
+            const unsigned hsh = vxb_drop_hash(rowh ^ ((unsigned)colb + cp));
             p0 = (hsh & 0xffffu) >= thr ? p0 : 0.f;
             p1 = (hsh >> 16) >= thr ? p1 : 0.f;
         }
@@ -630,25 +581,25 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
             f32x16 z;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            sn = f2_mma<MODE>(ones_frag(ktn, kbn), f2_from4(mslot, big2, 0u, 0u), z);
+            sn = vxb_mma<MODE>(ones_frag(ktn, kbn), vxb_from4(mslot, big2, 0u, 0u), z);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (i + 1 < 4) load_group(i + 1);
             if (HD_) {
                 const int ks = i >> 1, db = i & 1;
-                const bf16x8 ph = f2_from4(pp[0][4 * ks], pp[0][4 * ks + 1], pp[0][4 * ks + 2], pp[0][4 * ks + 3]);
-                const bf16x8 pl = f2_from4(pp[1][4 * ks], pp[1][4 * ks + 1], pp[1][4 * ks + 2], pp[1][4 * ks + 3]);
-                oacc[db] = f2_mma<MODE>(vl[i], ph, oacc[db]);
-                oacc[db] = f2_mma<MODE>(vh[i], pl, oacc[db]);
-                oacc[db] = f2_mma<MODE>(vh[i], ph, oacc[db]);
+                const bf16x8 ph = vxb_from4(pp[0][4 * ks], pp[0][4 * ks + 1], pp[0][4 * ks + 2], pp[0][4 * ks + 3]);
+                const bf16x8 pl = vxb_from4(pp[1][4 * ks], pp[1][4 * ks + 1], pp[1][4 * ks + 2], pp[1][4 * ks + 3]);
+                oacc[db] = vxb_mma<MODE>(vl[i], ph, oacc[db]);
+                oacc[db] = vxb_mma<MODE>(vh[i], pl, oacc[db]);
+                oacc[db] = vxb_mma<MODE>(vh[i], ph, oacc[db]);
             }
             if (HC) pair(colb, kbc, 2 * i, sc_, pc, ps);
             __builtin_amdgcn_sched_barrier(0);
             if (HN) {
-                sn = f2_mma<MODE>(kl[i], qfh[i], sn);
-                sn = f2_mma<MODE>(kh[i], qfl[i], sn);
-                sn = f2_mma<MODE>(kh[i], qfh[i], sn);
+                sn = vxb_mma<MODE>(kl[i], qfh[i], sn);
+                sn = vxb_mma<MODE>(kh[i], qfl[i], sn);
+                sn = vxb_mma<MODE>(kh[i], qfh[i], sn);
             }
             if (HC) pair(colb, kbc, 2 * i + 1, sc_, pc, ps);
             __builtin_amdgcn_sched_barrier(0);
@@ -679,7 +630,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
 
     // ---- prologue: unit 0's scores with m = 0 -> m = ceil(row maximum over the whole first TILE is not needed: unit 0 suffices)
     issue_kv(0, -1); issue_kv(1, 0); issue_kv(2, 1);
-    f2_wait_vm<2 * NLOAD>();                                // K0 landed ({K1 V0} {K2 V1} may be in flight)
+    vxb_wait_vm<2 * NLOAD>();                                // K0 landed ({K1 V0} {K2 V1} may be in flight)
     vxb_raw_barrier();
     f32x16 s_[2];
     unsigned pb[2][2][8];
@@ -705,7 +656,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
     // ---- region j = steps 2j + 1, 2j + 2: needs K(j + 1), V(j).  Top: {K(j+1), V(j)} landed; issue {K(j+3), V(j+2)}:
     //      K stage (j+3) % 3 held K(j) (read in region j-1), V stage (j+2) % 3 held V(j-1) (read in region j-1)
     for (int j = 0; j < nkt; ++j) {
-        f2_wait_vm<NLOAD>();
+        vxb_wait_vm<NLOAD>();
         vxb_raw_barrier();
         issue_kv(j + 3, j + 2);
         {
@@ -721,7 +672,7 @@ __global__ void __launch_bounds__(NW * 64, 2) flash2_fwd_x3_kernel(F3Args g) {
             step(F_, F_, T_, 0, 0, 0, 0, j, 1, s_[1], s_[0], pb[0], pb[1]);        // the last unit's P V product
         }
     }
-    f2_wait_vm<0>();
+    vxb_wait_vm<0>();
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (q_ok) {
@@ -787,7 +738,7 @@ __global__ void __launch_bounds__(256) split_f16_kernel(const float* __restrict_
         *reinterpret_cast<uint2*>(hi + r * cols + c4) = ph;
         if (lo) {
             float a0, a1, a2, a3;
-            f2_unpack<M_F16>(ph.x, a0, a1); f2_unpack<M_F16>(ph.y, a2, a3);
+            vxb_unpack<M_F16>(ph.x, a0, a1); vxb_unpack<M_F16>(ph.y, a2, a3);
             uint2 pl;
             pl.x = vxb_pack_f16(v.x - a0, v.y - a1); pl.y = vxb_pack_f16(v.z - a2, v.w - a3);
             *reinterpret_cast<uint2*>(lo + r * cols + c4) = pl;

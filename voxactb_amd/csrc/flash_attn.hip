@@ -20,12 +20,9 @@
 // carried as hi = bf16(a), lo = bf16(a - hi) and each product is evaluated as hi*hi + hi*lo + lo*hi (fp32 accumulate),
 // which keeps the fused kernels inside the 1e-4 Q-value bound of the exact-fp32 attention path.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int HD = 64;          // head dim
 constexpr int BQ = 128;         // queries per workgroup (4 waves x 32)
@@ -46,17 +43,6 @@ struct AttnArgs {
     unsigned seed;
 };
 
-__device__ __forceinline__ unsigned fa_hash(unsigned x) {
-    // one multiply round: the inputs are already products with odd constants; keep-rate, row / column sums and lag
-    // correlations of the 16-bit halves are indistinguishable from the two-round finaliser (checked offline on 4096 x 2048
-    // masks), and every hash costs a quarter-rate multiply less in the softmax loops
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return x;
-}
-// keep decisions for keys (2c, 2c+1) of row `row`: low / high 16 bits of one hash against thr = p * 65536
-__device__ __forceinline__ unsigned fa_keep_pair(unsigned seed, unsigned row, unsigned colpair) {
-    return fa_hash((row * 0x9E3779B1U + seed) ^ (colpair * 0x85EBCA77U + 0xC2B2AE3DU));
-}
 __device__ __forceinline__ unsigned fa_pack2(float lo, float hi) { return vxb_pack_bf16(lo, hi); }
 // hi/lo split of a value pair: ph = bf16 pair, pl = bf16 pair of the (exact) residuals
 __device__ __forceinline__ void fa_split2(float a, float b, unsigned& ph, unsigned& pl) {
@@ -67,32 +53,6 @@ __device__ __forceinline__ unsigned long long fa_tr16(unsigned addr) {
     unsigned long long v;
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
     return v;
-}
-// acc += A B with A = ah + al, B = bh + bl (X3) or A = ah, B = bh
-template <int X3>
-__device__ __forceinline__ f32x16 fa_mma(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
-    if (X3) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
-// 8 consecutive fp32 (two float4) -> one bf16x8 fragment (+ residual fragment), optionally pre-scaled
-template <int X3>
-__device__ __forceinline__ void fa_frag8(const float* p, float s, bf16x8& fh, bf16x8& fl) {
-    union { unsigned u[4]; bf16x8 v; } h, l;
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    const float4 c = *reinterpret_cast<const float4*>(p + 4);
-    if (X3) {
-        fa_split2(a.x * s, a.y * s, h.u[0], l.u[0]); fa_split2(a.z * s, a.w * s, h.u[1], l.u[1]);
-        fa_split2(c.x * s, c.y * s, h.u[2], l.u[2]); fa_split2(c.z * s, c.w * s, h.u[3], l.u[3]);
-        fl = l.v;
-    } else {
-        h.u[0] = fa_pack2(a.x * s, a.y * s); h.u[1] = fa_pack2(a.z * s, a.w * s);
-        h.u[2] = fa_pack2(c.x * s, c.y * s); h.u[3] = fa_pack2(c.z * s, c.w * s);
-        fl = h.v;
-    }
-    fh = h.v;
 }
 // one float4 -> 8-byte bf16 store into a plane (and its residual into the lo plane PL u16 further)
 template <int X3>
@@ -105,16 +65,6 @@ __device__ __forceinline__ void fa_store4(u16* dst, int PL, const float4 v, floa
         ph.x = fa_pack2(v.x * s, v.y * s); ph.y = fa_pack2(v.z * s, v.w * s);
     }
     *reinterpret_cast<uint2*>(dst) = ph;
-}
-__device__ __forceinline__ bf16x8 fa_join(unsigned long long a, unsigned long long b) {
-    union { unsigned long long u[2]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b;
-    return t.v;
-}
-__device__ __forceinline__ bf16x8 fa_from4(const unsigned* p) {
-    union { unsigned u[4]; bf16x8 v; } t;
-    t.u[0] = p[0]; t.u[1] = p[1]; t.u[2] = p[2]; t.u[3] = p[3];
-    return t.v;
 }
 
 template <int X3>
@@ -136,7 +86,7 @@ __global__ void __launch_bounds__(256) flash_fwd_kernel(AttnArgs g) {
     // Q^T fragments: lane (q, hi) holds q[16 ks + 8 hi .. +8] for ks = 0..3
     bf16x8 qfh[4], qfl[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fa_frag8<X3>(qp + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
+    for (int ks = 0; ks < 4; ++ks) vxb_frag8<X3>(qp + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
     f32x16 oacc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -196,7 +146,7 @@ __global__ void __launch_bounds__(256) flash_fwd_kernel(AttnArgs g) {
                 const u16* kp = &Ks[(kb * 32 + lq) * LDK + 16 * ks + 8 * hi];
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(kp);
                 const bf16x8 al = *reinterpret_cast<const bf16x8*>(kp + X3 * KPL);
-                sacc[kb] = fa_mma<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
+                sacc[kb] = vxb_mma_x3<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
             }
         }
         // sacc[kb][r] = score(key = kt*64 + kb*32 + (r&3) + 8*(r>>2) + 4*hi, q = this lane's query), log2 domain
@@ -224,7 +174,7 @@ __global__ void __launch_bounds__(256) flash_fwd_kernel(AttnArgs g) {
                 psum += p0 + p1;
                 if (thr > 0u) {
                     const unsigned key = (unsigned)(kbase_t + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi);
-                    const unsigned hsh = fa_keep_pair(g.seed, row_id, key >> 1);
+                    const unsigned hsh = vxb_drop_keep_pair(g.seed, row_id, key >> 1);
                     p0 = (hsh & 0xffffu) >= thr ? p0 * keep_scale : 0.f;
                     p1 = (hsh >> 16) >= thr ? p1 * keep_scale : 0.f;
                 }
@@ -241,8 +191,8 @@ __global__ void __launch_bounds__(256) flash_fwd_kernel(AttnArgs g) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 pfh = fa_from4(&pbh[kb][4 * ks]);
-                const bf16x8 pfl = X3 ? fa_from4(&pbl[kb][4 * ks]) : pfh;
+                const bf16x8 pfh = vxb_from4(&pbh[kb][4 * ks]);
+                const bf16x8 pfl = X3 ? vxb_from4(&pbl[kb][4 * ks]) : pfh;
                 unsigned long long va[2][2], vl[2][2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
@@ -258,9 +208,9 @@ __global__ void __launch_bounds__(256) flash_fwd_kernel(AttnArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 vfh = fa_join(va[db][0], va[db][1]);
-                    const bf16x8 vfl = X3 ? fa_join(vl[db][0], vl[db][1]) : vfh;
-                    oacc[db] = fa_mma<X3>(vfh, vfl, pfh, pfl, oacc[db]);
+                    const bf16x8 vfh = vxb_join(va[db][0], va[db][1]);
+                    const bf16x8 vfl = X3 ? vxb_join(vl[db][0], vl[db][1]) : vfh;
+                    oacc[db] = vxb_mma_x3<X3>(vfh, vfl, pfh, pfl, oacc[db]);
                 }
             }
     }
@@ -340,8 +290,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dq_kernel(AttnBwdArgs g) {
     bf16x8 qfh[4], qfl[4], dofh[4], dofl[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        fa_frag8<X3>(g.q + qoff + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
-        fa_frag8<X3>(g.d_o + qoff + 16 * ks + 8 * hi, 1.f, dofh[ks], dofl[ks]);
+        vxb_frag8<X3>(g.q + qoff + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
+        vxb_frag8<X3>(g.d_o + qoff + 16 * ks + 8 * hi, 1.f, dofh[ks], dofl[ks]);
     }
     const float lse2 = q_ok ? g.lse[(long long)bh * g.Nq + qrow] * LOG2E : 0.f;
     const float dsum = q_ok ? g.dsum[(long long)bh * g.Nq + qrow] : 0.f;
@@ -400,8 +350,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dq_kernel(AttnBwdArgs g) {
                 const u16* vp = &Vb[(kb * 32 + lq) * LDK + 16 * ks + 8 * hi];
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(kp), al = *reinterpret_cast<const bf16x8*>(kp + X3 * KPL);
                 const bf16x8 ch = *reinterpret_cast<const bf16x8*>(vp), cl = *reinterpret_cast<const bf16x8*>(vp + X3 * KPL);
-                sacc[kb] = fa_mma<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
-                pacc[kb] = fa_mma<X3>(ch, cl, dofh[ks], dofl[ks], pacc[kb]);
+                sacc[kb] = vxb_mma_x3<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
+                pacc[kb] = vxb_mma_x3<X3>(ch, cl, dofh[ks], dofl[ks], pacc[kb]);
             }
         }
         const int kbase_t = kt * BKV;
@@ -415,7 +365,7 @@ __global__ void __launch_bounds__(256) flash_bwd_dq_kernel(AttnBwdArgs g) {
                 float p1 = key + 1 < g.Nk ? exp2f(sacc[kb][r + 1] - lse2) : 0.f;
                 float d0 = pacc[kb][r], d1 = pacc[kb][r + 1];
                 if (thr > 0u) {
-                    const unsigned hsh = fa_keep_pair(g.seed, row_id, (unsigned)key >> 1);
+                    const unsigned hsh = vxb_drop_keep_pair(g.seed, row_id, (unsigned)key >> 1);
                     d0 = (hsh & 0xffffu) >= thr ? d0 * keep_scale : 0.f;
                     d1 = (hsh >> 16) >= thr ? d1 * keep_scale : 0.f;
                 }
@@ -427,8 +377,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dq_kernel(AttnBwdArgs g) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 sfh = fa_from4(&sbh[kb][4 * ks]);
-                const bf16x8 sfl = X3 ? fa_from4(&sbl[kb][4 * ks]) : sfh;
+                const bf16x8 sfh = vxb_from4(&sbh[kb][4 * ks]);
+                const bf16x8 sfl = X3 ? vxb_from4(&sbl[kb][4 * ks]) : sfh;
                 unsigned long long ka[2][2], kl[2][2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
@@ -444,9 +394,9 @@ __global__ void __launch_bounds__(256) flash_bwd_dq_kernel(AttnBwdArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 kfh = fa_join(ka[db][0], ka[db][1]);
-                    const bf16x8 kfl = X3 ? fa_join(kl[db][0], kl[db][1]) : kfh;
-                    dqacc[db] = fa_mma<X3>(kfh, kfl, sfh, sfl, dqacc[db]);
+                    const bf16x8 kfh = vxb_join(ka[db][0], ka[db][1]);
+                    const bf16x8 kfl = X3 ? vxb_join(kl[db][0], kl[db][1]) : kfh;
+                    dqacc[db] = vxb_mma_x3<X3>(kfh, kfl, sfh, sfl, dqacc[db]);
                 }
             }
     }
@@ -486,8 +436,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dkv_kernel(AttnBwdArgs g) {
     bf16x8 kfh[4], kfl[4], vfh[4], vfl[4];     // K^T / V^T fragments: lane (key, hi) holds k[16 ks + 8 hi .. +8]
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        fa_frag8<X3>(g.kv + koff + 16 * ks + 8 * hi, 1.f, kfh[ks], kfl[ks]);
-        fa_frag8<X3>(g.kv + koff + inner + 16 * ks + 8 * hi, 1.f, vfh[ks], vfl[ks]);
+        vxb_frag8<X3>(g.kv + koff + 16 * ks + 8 * hi, 1.f, kfh[ks], kfl[ks]);
+        vxb_frag8<X3>(g.kv + koff + inner + 16 * ks + 8 * hi, 1.f, vfh[ks], vfl[ks]);
     }
     f32x16 dkacc[2], dvacc[2];
 #pragma unroll
@@ -554,8 +504,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dkv_kernel(AttnBwdArgs g) {
                 const u16* op = &Ob[(qb * 32 + lk) * LDK + 16 * ks + 8 * hi];
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(qp), al = *reinterpret_cast<const bf16x8*>(qp + X3 * KPL);
                 const bf16x8 ch = *reinterpret_cast<const bf16x8*>(op), cl = *reinterpret_cast<const bf16x8*>(op + X3 * KPL);
-                sacc[qb] = fa_mma<X3>(ah, al, kfh[ks], kfl[ks], sacc[qb]);
-                pacc[qb] = fa_mma<X3>(ch, cl, vfh[ks], vfl[ks], pacc[qb]);
+                sacc[qb] = vxb_mma_x3<X3>(ah, al, kfh[ks], kfl[ks], sacc[qb]);
+                pacc[qb] = vxb_mma_x3<X3>(ch, cl, vfh[ks], vfl[ks], pacc[qb]);
             }
         }
         // sacc[qb][r] = S[q = qt*64 + qb*32 + (r&3) + 8*(r>>2) + 4*hi][key = this lane's key]
@@ -571,8 +521,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dkv_kernel(AttnBwdArgs g) {
                 float pd0 = p0, pd1 = p1;
                 if (thr > 0u) {
                     const unsigned row0 = (unsigned)bh * (unsigned)g.Nq + (unsigned)(qt * BKV + ql);
-                    const unsigned h0 = fa_keep_pair(g.seed, row0, (unsigned)key >> 1);
-                    const unsigned h1 = fa_keep_pair(g.seed, row0 + 1u, (unsigned)key >> 1);
+                    const unsigned h0 = vxb_drop_keep_pair(g.seed, row0, (unsigned)key >> 1);
+                    const unsigned h1 = vxb_drop_keep_pair(g.seed, row0 + 1u, (unsigned)key >> 1);
                     const bool k0 = ((key & 1) ? (h0 >> 16) : (h0 & 0xffffu)) >= thr;
                     const bool k1 = ((key & 1) ? (h1 >> 16) : (h1 & 0xffffu)) >= thr;
                     d0 = k0 ? d0 * keep_scale : 0.f; d1 = k1 ? d1 * keep_scale : 0.f;
@@ -592,8 +542,8 @@ __global__ void __launch_bounds__(256) flash_bwd_dkv_kernel(AttnBwdArgs g) {
         for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 pfh = fa_from4(&pbh[qb][4 * ks]), sfh = fa_from4(&sbh[qb][4 * ks]);
-                const bf16x8 pfl = X3 ? fa_from4(&pbl[qb][4 * ks]) : pfh, sfl = X3 ? fa_from4(&sbl[qb][4 * ks]) : sfh;
+                const bf16x8 pfh = vxb_from4(&pbh[qb][4 * ks]), sfh = vxb_from4(&sbh[qb][4 * ks]);
+                const bf16x8 pfl = X3 ? vxb_from4(&pbl[qb][4 * ks]) : pfh, sfl = X3 ? vxb_from4(&sbl[qb][4 * ks]) : sfh;
                 unsigned long long oa[2][2], qa[2][2], ol[2][2], ql2[2][2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
@@ -613,10 +563,10 @@ __global__ void __launch_bounds__(256) flash_bwd_dkv_kernel(AttnBwdArgs g) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 ofh = fa_join(oa[db][0], oa[db][1]), q2h = fa_join(qa[db][0], qa[db][1]);
-                    const bf16x8 ofl = X3 ? fa_join(ol[db][0], ol[db][1]) : ofh, q2l = X3 ? fa_join(ql2[db][0], ql2[db][1]) : q2h;
-                    dvacc[db] = fa_mma<X3>(pfh, pfl, ofh, ofl, dvacc[db]);
-                    dkacc[db] = fa_mma<X3>(sfh, sfl, q2h, q2l, dkacc[db]);
+                    const bf16x8 ofh = vxb_join(oa[db][0], oa[db][1]), q2h = vxb_join(qa[db][0], qa[db][1]);
+                    const bf16x8 ofl = X3 ? vxb_join(ol[db][0], ol[db][1]) : ofh, q2l = X3 ? vxb_join(ql2[db][0], ql2[db][1]) : q2h;
+                    dvacc[db] = vxb_mma_x3<X3>(pfh, pfl, ofh, ofl, dvacc[db]);
+                    dkacc[db] = vxb_mma_x3<X3>(sfh, sfl, q2h, q2l, dkacc[db]);
                 }
             }
     }

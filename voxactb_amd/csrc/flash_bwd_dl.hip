@@ -6,12 +6,9 @@
 // XOR-swizzled with f(row) = rotate-right of ((row >> 1) & 7), which is conflict-free for both (the 16 rows of a b128
 // service group get 8 distinct keys per row parity; the even rows r, r+2 of a transposed read differ in the key's 4-bit).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int HD = 64, BQ = 128, BT = 64;
 constexpr int TILE = BT * HD;               // u16 per plane tile (8 KB)
@@ -34,71 +31,6 @@ struct BdArgs {
     unsigned seed;
 };
 
-__device__ __forceinline__ unsigned bd_hash(unsigned x) {
-    // one multiply round: the inputs are already products with odd constants; keep-rate, row / column sums and lag
-    // correlations of the 16-bit halves are indistinguishable from the two-round finaliser (checked offline on 4096 x 2048
-    // masks), and every hash costs a quarter-rate multiply less in the softmax loops
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return x;
-}
-__device__ __forceinline__ unsigned bd_keep_pair(unsigned seed, unsigned row, unsigned colpair) {     // == fa_keep_pair
-    return bd_hash((row * 0x9E3779B1U + seed) ^ (colpair * 0x85EBCA77U + 0xC2B2AE3DU));
-}
-__device__ __forceinline__ void bd_split2(float a, float b, unsigned& ph, unsigned& pl) {
-    ph = vxb_pack_bf16(a, b);
-    pl = vxb_pack_bf16(a - __uint_as_float(ph << 16), b - __uint_as_float(ph & 0xffff0000u));
-}
-__device__ __forceinline__ bf16x8 bd_from4(const unsigned* p) {
-    union { unsigned u[4]; bf16x8 v; } t;
-    t.u[0] = p[0]; t.u[1] = p[1]; t.u[2] = p[2]; t.u[3] = p[3];
-    return t.v;
-}
-__device__ __forceinline__ bf16x8 bd_join(unsigned long long a, unsigned long long b) {
-    union { unsigned long long u[2]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b;
-    return t.v;
-}
-typedef short bd_v4s __attribute__((ext_vector_type(4)));
-// transposed 8-byte LDS read through the compiler builtin (lane base + immediate offset, compiler-placed waits)
-__device__ __forceinline__ unsigned long long bd_tr16(const u16* p) {
-    union { bd_v4s v; unsigned long long u; } t;
-    t.v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bd_v4s*)p);
-    return t.u;
-}
-template <int X3>
-__device__ __forceinline__ f32x16 bd_mma(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
-    if (X3) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
-__device__ __forceinline__ void bd_load16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ int bd_swz(int row) {           // chunk XOR key of a tile row
-    const int x = (row >> 1) & 7;
-    return ((x & 1) << 2) | (x >> 1);
-}
-// 8 consecutive fp32 -> bf16x8 fragment (+ residual), pre-scaled
-template <int X3>
-__device__ __forceinline__ void bd_frag8(const float* p, float s, bf16x8& fh, bf16x8& fl) {
-    union { unsigned u[4]; bf16x8 v; } h, l;
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    const float4 c = *reinterpret_cast<const float4*>(p + 4);
-    if (X3) {
-        bd_split2(a.x * s, a.y * s, h.u[0], l.u[0]); bd_split2(a.z * s, a.w * s, h.u[1], l.u[1]);
-        bd_split2(c.x * s, c.y * s, h.u[2], l.u[2]); bd_split2(c.z * s, c.w * s, h.u[3], l.u[3]);
-        fl = l.v;
-    } else {
-        h.u[0] = vxb_pack_bf16(a.x * s, a.y * s); h.u[1] = vxb_pack_bf16(a.z * s, a.w * s);
-        h.u[2] = vxb_pack_bf16(c.x * s, c.y * s); h.u[3] = vxb_pack_bf16(c.z * s, c.w * s);
-        fl = h.v;
-    }
-    fh = h.v;
-}
-
 // ------------------------------------------------------------------------------------------------ dQ
 // lane = query (swapped form).  Per K/V tile: S^T = K Q^T, P = exp2(S^T - lse); dP^T = V dO^T;
 // dS^T = scale * P * (dP * keep/(1-p) - D); dQ^T += K^T dS^T (K^T by transposed reads of the same K tile).
@@ -119,8 +51,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
     bf16x8 qfh[4], qfl[4], dofh[4], dofl[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        bd_frag8<X3>(g.q + qoff + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
-        bd_frag8<X3>(g.d_o + qoff + 16 * ks + 8 * hi, 1.f, dofh[ks], dofl[ks]);
+        vxb_frag8<X3>(g.q + qoff + 16 * ks + 8 * hi, qs, qfh[ks], qfl[ks]);
+        vxb_frag8<X3>(g.d_o + qoff + 16 * ks + 8 * hi, 1.f, dofh[ks], dofl[ks]);
     }
     const float lse2 = q_ok ? g.lse[(long long)bh * g.Nq + qrow] * LOG2E : 0.f;
     const float dsum = q_ok ? g.dsum[(long long)bh * g.Nq + qrow] : 0.f;
@@ -135,7 +67,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         lkey[i] = (2 * wid + i) * 8 + (lane >> 3);
-        lch[i] = (lane & 7) ^ bd_swz(lkey[i]);
+        lch[i] = (lane & 7) ^ vxb_swz(lkey[i]);
     }
     auto issue = [&](int stage, int kt) {
         u16* sb = smem + stage * STAGE;
@@ -145,8 +77,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
             const u16* rowp = g.kvp + (kv_row0 + key) * (2 * inner) + h * HD + lch[i] * 8;
 #pragma unroll
             for (int p = 0; p < NPL; ++p) {
-                bd_load16(rowp + p * g.kv_plane, sb + p * TILE + (2 * wid + i) * 512);
-                bd_load16(rowp + p * g.kv_plane + inner, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(rowp + p * g.kv_plane, sb + p * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(rowp + p * g.kv_plane + inner, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
             }
         }
     };
@@ -155,7 +87,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
     const unsigned row_id = (unsigned)bh * (unsigned)g.Nq + (unsigned)qrow;
     int rbase[2], rkey[2];
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) { const int row = kb * 32 + lq; rbase[kb] = row * 64; rkey[kb] = bd_swz(row); }
+    for (int kb = 0; kb < 2; ++kb) { const int row = kb * 32 + lq; rbase[kb] = row * 64; rkey[kb] = vxb_swz(row); }
     const int t16 = lane & 15, gq = lane >> 4;
     const int trow0 = 4 * (gq >> 1) + (t16 >> 2);
     const int tchunk0 = 2 * (gq & 1) + ((t16 & 3) >> 1), thalf = (t16 & 1) * 4;
@@ -166,7 +98,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
     for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ bd_swz(8 * rr + trow0)) * 8 + thalf;
+            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ vxb_swz(8 * rr + trow0)) * 8 + thalf;
 
     const int nkt = (g.Nk + BT - 1) / BT;
     issue(0, 0);
@@ -187,8 +119,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(sb + co), al = *reinterpret_cast<const bf16x8*>(sb + X3 * TILE + co);
                 const bf16x8 ch = *reinterpret_cast<const bf16x8*>(sb + NPL * TILE + co);
                 const bf16x8 cl = *reinterpret_cast<const bf16x8*>(sb + (NPL + X3) * TILE + co);
-                sacc[kb] = bd_mma<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
-                pacc[kb] = bd_mma<X3>(ch, cl, dofh[ks], dofl[ks], pacc[kb]);
+                sacc[kb] = vxb_mma_x3<X3>(ah, al, qfh[ks], qfl[ks], sacc[kb]);
+                pacc[kb] = vxb_mma_x3<X3>(ch, cl, dofh[ks], dofl[ks], pacc[kb]);
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -203,34 +135,34 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dq_dl_kernel(BdArgs g) {
                 float p1 = key + 1 < g.Nk ? __builtin_amdgcn_exp2f(sacc[kb][r + 1] - lse2) : 0.f;
                 float d0 = pacc[kb][r], d1 = pacc[kb][r + 1];
                 if (DROP) {
-                    const unsigned hsh = bd_keep_pair(g.seed, row_id, (unsigned)key >> 1);
+                    const unsigned hsh = vxb_drop_keep_pair(g.seed, row_id, (unsigned)key >> 1);
                     d0 = (hsh & 0xffffu) >= thr ? d0 * keep_scale : 0.f;
                     d1 = (hsh >> 16) >= thr ? d1 * keep_scale : 0.f;
                 }
                 const float s0 = g.scale * p0 * (d0 - dsum), s1 = g.scale * p1 * (d1 - dsum);
-                if (X3) bd_split2(s0, s1, sbh[kb][r >> 1], sbl[kb][r >> 1]);
+                if (X3) vxb_split2(s0, s1, sbh[kb][r >> 1], sbl[kb][r >> 1]);
                 else sbh[kb][r >> 1] = vxb_pack_bf16(s0, s1);
             }
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 sfh = bd_from4(&sbh[kb][4 * ks]);
-                const bf16x8 sfl = X3 ? bd_from4(&sbl[kb][4 * ks]) : sfh;
+                const bf16x8 sfh = vxb_from4(&sbh[kb][4 * ks]);
+                const bf16x8 sfl = X3 ? vxb_from4(&sbl[kb][4 * ks]) : sfh;
                 unsigned long long ka[2][2], kl[2][2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db)
 #pragma unroll
                     for (int rr = 0; rr < 2; ++rr) {
                         const u16* ad = sb + tlane[db][rr] + (kb * 32 + 16 * ks + 8 * rr) * 64;
-                        ka[db][rr] = bd_tr16(ad);
-                        if (X3) kl[db][rr] = bd_tr16(ad + TILE);
+                        ka[db][rr] = vxb_tr16(ad);
+                        if (X3) kl[db][rr] = vxb_tr16(ad + TILE);
                     }
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 kfh = bd_join(ka[db][0], ka[db][1]);
-                    const bf16x8 kfl = X3 ? bd_join(kl[db][0], kl[db][1]) : kfh;
-                    dqacc[db] = bd_mma<X3>(kfh, kfl, sfh, sfl, dqacc[db]);
+                    const bf16x8 kfh = vxb_join(ka[db][0], ka[db][1]);
+                    const bf16x8 kfl = X3 ? vxb_join(kl[db][0], kl[db][1]) : kfh;
+                    dqacc[db] = vxb_mma_x3<X3>(kfh, kfl, sfh, sfl, dqacc[db]);
                 }
             }
     }
@@ -268,8 +200,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
     bf16x8 kfh[4], kfl[4], vfh[4], vfl[4];     // K^T (x scale log2e) / V^T fragments: lane (key, hi) holds k[16 ks + 8 hi .. +8]
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        bd_frag8<X3>(g.kv + koff + 16 * ks + 8 * hi, qs, kfh[ks], kfl[ks]);
-        bd_frag8<X3>(g.kv + koff + inner + 16 * ks + 8 * hi, 1.f, vfh[ks], vfl[ks]);
+        vxb_frag8<X3>(g.kv + koff + 16 * ks + 8 * hi, qs, kfh[ks], kfl[ks]);
+        vxb_frag8<X3>(g.kv + koff + inner + 16 * ks + 8 * hi, 1.f, vfh[ks], vfl[ks]);
     }
     f32x16 dkacc[2], dvacc[2];
 #pragma unroll
@@ -282,7 +214,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         lrow[i] = (2 * wid + i) * 8 + (lane >> 3);
-        lch[i] = (lane & 7) ^ bd_swz(lrow[i]);
+        lch[i] = (lane & 7) ^ vxb_swz(lrow[i]);
     }
     auto issue = [&](int stage, int qt) {
         u16* sb = smem + stage * STAGE;
@@ -292,8 +224,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
             const long long ro = (q_row0 + qq) * inner + h * HD + lch[i] * 8;
 #pragma unroll
             for (int p = 0; p < NPL; ++p) {
-                bd_load16(g.qp + p * g.q_plane + ro, sb + p * TILE + (2 * wid + i) * 512);
-                bd_load16(g.dop + p * g.q_plane + ro, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(g.qp + p * g.q_plane + ro, sb + p * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(g.dop + p * g.q_plane + ro, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
             }
         }
         if (tid < BT) {
@@ -315,7 +247,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
     for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ bd_swz(8 * rr + trow0)) * 8 + thalf;
+            tlane[db][rr] = trow0 * 64 + ((tchunk0 + 4 * db) ^ vxb_swz(8 * rr + trow0)) * 8 + thalf;
 
     const int nqt = (g.Nq + BT - 1) / BT;
     issue(0, 0);
@@ -336,15 +268,15 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
             const int arow = qb * 32 + lk;
-            const int abase = arow * 64, akey = bd_swz(arow);
+            const int abase = arow * 64, akey = vxb_swz(arow);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int co = abase + ((2 * ks + hi) ^ akey) * 8;
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(sb + co), al = *reinterpret_cast<const bf16x8*>(sb + X3 * TILE + co);
                 const bf16x8 ch = *reinterpret_cast<const bf16x8*>(sb + NPL * TILE + co);
                 const bf16x8 cl = *reinterpret_cast<const bf16x8*>(sb + (NPL + X3) * TILE + co);
-                sacc = bd_mma<X3>(ah, al, kfh[ks], kfl[ks], sacc);
-                pacc = bd_mma<X3>(ch, cl, vfh[ks], vfl[ks], pacc);
+                sacc = vxb_mma_x3<X3>(ah, al, kfh[ks], kfl[ks], sacc);
+                pacc = vxb_mma_x3<X3>(ch, cl, vfh[ks], vfl[ks], pacc);
             }
             __builtin_amdgcn_s_setprio(0);
             // sacc[r] = S[q = qt*64 + qb*32 + (r&3) + 8*(r>>2) + 4*hi][key = this lane's key]
@@ -360,7 +292,7 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
                     const unsigned row0 = (unsigned)bh * (unsigned)g.Nq + (unsigned)(qt * BT + ql);
                     // the mask word of (row, key pair) covers this lane's key and its neighbour's (lane ^ 1): the even lane
                     // hashes row0, the odd lane row0 + 1 and the two swap words (one DPP move) instead of hashing both
-                    const unsigned hm = bd_keep_pair(g.seed, row0 + kodd, (unsigned)key >> 1);
+                    const unsigned hm = vxb_drop_keep_pair(g.seed, row0 + kodd, (unsigned)key >> 1);
                     const unsigned ho = (unsigned)__builtin_amdgcn_mov_dpp((int)hm, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
                     const unsigned h0 = kodd ? ho : hm, h1 = kodd ? hm : ho;
                     const bool k0 = (h0 << hshift) >= thr16, k1 = (h1 << hshift) >= thr16;      // this key's 16-bit half >= thr
@@ -369,8 +301,8 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
                 }
                 const float s0 = g.scale * p0 * (d0 - s_dsum[st][ql]), s1 = g.scale * p1 * (d1 - s_dsum[st][ql + 1]);
                 if (X3) {
-                    bd_split2(pd0, pd1, pbh[r >> 1], pbl[r >> 1]);
-                    bd_split2(s0, s1, sbh[r >> 1], sbl[r >> 1]);
+                    vxb_split2(pd0, pd1, pbh[r >> 1], pbl[r >> 1]);
+                    vxb_split2(s0, s1, sbh[r >> 1], sbl[r >> 1]);
                 } else {
                     pbh[r >> 1] = vxb_pack_bf16(pd0, pd1);
                     sbh[r >> 1] = vxb_pack_bf16(s0, s1);
@@ -379,27 +311,27 @@ __global__ void __launch_bounds__(256, 2) flash_bwd_dkv_dl_kernel(BdArgs g) {
             // dV += Pd^T dO ; dK += dS^T Q : contraction over this block's 32 queries = 2 k-steps of 16
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 pfh = bd_from4(&pbh[4 * ks]), sfh = bd_from4(&sbh[4 * ks]);
-                const bf16x8 pfl = X3 ? bd_from4(&pbl[4 * ks]) : pfh, sfl = X3 ? bd_from4(&sbl[4 * ks]) : sfh;
+                const bf16x8 pfh = vxb_from4(&pbh[4 * ks]), sfh = vxb_from4(&sbh[4 * ks]);
+                const bf16x8 pfl = X3 ? vxb_from4(&pbl[4 * ks]) : pfh, sfl = X3 ? vxb_from4(&sbl[4 * ks]) : sfh;
                 unsigned long long oa[2][2], qa[2][2], ol[2][2], ql2[2][2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db)
 #pragma unroll
                     for (int rr = 0; rr < 2; ++rr) {
                         const int off = qb * 32 * 64 + tlane[db][rr] + (16 * ks + 8 * rr) * 64;
-                        oa[db][rr] = bd_tr16(o_t + off);
-                        qa[db][rr] = bd_tr16(q_t + off);
+                        oa[db][rr] = vxb_tr16(o_t + off);
+                        qa[db][rr] = vxb_tr16(q_t + off);
                         if (X3) {
-                            ol[db][rr] = bd_tr16(o_t + off + TILE);
-                            ql2[db][rr] = bd_tr16(q_t + off + TILE);
+                            ol[db][rr] = vxb_tr16(o_t + off + TILE);
+                            ql2[db][rr] = vxb_tr16(q_t + off + TILE);
                         }
                     }
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 ofh = bd_join(oa[db][0], oa[db][1]), q2h = bd_join(qa[db][0], qa[db][1]);
-                    const bf16x8 ofl = X3 ? bd_join(ol[db][0], ol[db][1]) : ofh, q2l = X3 ? bd_join(ql2[db][0], ql2[db][1]) : q2h;
-                    dvacc[db] = bd_mma<X3>(pfh, pfl, ofh, ofl, dvacc[db]);
-                    dkacc[db] = bd_mma<X3>(sfh, sfl, q2h, q2l, dkacc[db]);
+                    const bf16x8 ofh = vxb_join(oa[db][0], oa[db][1]), q2h = vxb_join(qa[db][0], qa[db][1]);
+                    const bf16x8 ofl = X3 ? vxb_join(ol[db][0], ol[db][1]) : ofh, q2l = X3 ? vxb_join(ql2[db][0], ql2[db][1]) : q2h;
+                    dvacc[db] = vxb_mma_x3<X3>(pfh, pfl, ofh, ofl, dvacc[db]);
+                    dkacc[db] = vxb_mma_x3<X3>(sfh, sfl, q2h, q2l, dkacc[db]);
                 }
             }
         }

@@ -9,12 +9,9 @@
 // side: K (read by ds_read_b128, 32 keys x one chunk per half wave) with key (row >> 1) & 7, V (read transposed by
 // ds_read_b64_tr_b16, 8 keys x 64 bytes per half wave) with key 4 * ((row >> 1) & 1) -- both conflict-free.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int HD = 64, BQ = 128, BKV = 64;
 constexpr int TILE = BKV * HD;              // u16 per K or V plane tile (8 KB)
@@ -30,51 +27,6 @@ struct FdArgs {
     float scale, p_drop;
     unsigned seed;
 };
-
-__device__ __forceinline__ unsigned fd_hash(unsigned x) {
-    // one multiply round: the inputs are already products with odd constants; keep-rate, row / column sums and lag
-    // correlations of the 16-bit halves are indistinguishable from the two-round finaliser (checked offline on 4096 x 2048
-    // masks), and every hash costs a quarter-rate multiply less in the softmax loops
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return x;
-}
-__device__ __forceinline__ unsigned fd_keep_pair(unsigned seed, unsigned row, unsigned colpair) {     // == fa_keep_pair
-    return fd_hash((row * 0x9E3779B1U + seed) ^ (colpair * 0x85EBCA77U + 0xC2B2AE3DU));
-}
-__device__ __forceinline__ void fd_split2(float a, float b, unsigned& ph, unsigned& pl) {
-    ph = vxb_pack_bf16(a, b);
-    pl = vxb_pack_bf16(a - __uint_as_float(ph << 16), b - __uint_as_float(ph & 0xffff0000u));
-}
-__device__ __forceinline__ bf16x8 fd_from4(const unsigned* p) {
-    union { unsigned u[4]; bf16x8 v; } t;
-    t.u[0] = p[0]; t.u[1] = p[1]; t.u[2] = p[2]; t.u[3] = p[3];
-    return t.v;
-}
-__device__ __forceinline__ bf16x8 fd_join(unsigned long long a, unsigned long long b) {
-    union { unsigned long long u[2]; bf16x8 v; } t;
-    t.u[0] = a; t.u[1] = b;
-    return t.v;
-}
-typedef short fd_v4s __attribute__((ext_vector_type(4)));
-// transposed 8-byte LDS read through the compiler builtin: a lane base + compile-time offset folds into the instruction's
-// immediate (no address arithmetic per read) and the compiler places the waits
-__device__ __forceinline__ unsigned long long fd_tr16(const u16* p) {
-    union { fd_v4s v; unsigned long long u; } t;
-    t.v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fd_v4s*)p);
-    return t.u;
-}
-template <int X3>
-__device__ __forceinline__ f32x16 fd_mma(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
-    if (X3) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-}
-__device__ __forceinline__ void fd_load16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 template <int X3, int DROP>
 __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
@@ -99,8 +51,8 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
         const float4 a = *reinterpret_cast<const float4*>(qp + 16 * ks + 8 * hi);
         const float4 c = *reinterpret_cast<const float4*>(qp + 16 * ks + 8 * hi + 4);
         if (X3) {
-            fd_split2(a.x * qs, a.y * qs, th.u[0], tl.u[0]); fd_split2(a.z * qs, a.w * qs, th.u[1], tl.u[1]);
-            fd_split2(c.x * qs, c.y * qs, th.u[2], tl.u[2]); fd_split2(c.z * qs, c.w * qs, th.u[3], tl.u[3]);
+            vxb_split2(a.x * qs, a.y * qs, th.u[0], tl.u[0]); vxb_split2(a.z * qs, a.w * qs, th.u[1], tl.u[1]);
+            vxb_split2(c.x * qs, c.y * qs, th.u[2], tl.u[2]); vxb_split2(c.z * qs, c.w * qs, th.u[3], tl.u[3]);
         } else {
             th.u[0] = vxb_pack_bf16(a.x * qs, a.y * qs); th.u[1] = vxb_pack_bf16(a.z * qs, a.w * qs);
             th.u[2] = vxb_pack_bf16(c.x * qs, c.y * qs); th.u[3] = vxb_pack_bf16(c.z * qs, c.w * qs);
@@ -133,8 +85,8 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
             const u16* rowp = g.kv + (kv_row0 + key) * (2 * inner) + h * HD;
 #pragma unroll
             for (int p = 0; p < NPL; ++p) {
-                fd_load16(rowp + p * g.kv_plane + kch[i] * 8, sb + p * TILE + (2 * wid + i) * 512);
-                fd_load16(rowp + p * g.kv_plane + inner + vch[i] * 8, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(rowp + p * g.kv_plane + kch[i] * 8, sb + p * TILE + (2 * wid + i) * 512);
+                vxb_load_lds16(rowp + p * g.kv_plane + inner + vch[i] * 8, sb + (NPL + p) * TILE + (2 * wid + i) * 512);
             }
         }
     };
@@ -183,7 +135,7 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
             }
             __builtin_amdgcn_sched_barrier(0);          // (without it the scheduler sinks every read next to its MFMA again)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) sacc[kb] = fd_mma<X3>(ahf[ks], alf[ks], qfh[ks], qfl[ks], sacc[kb]);
+            for (int ks = 0; ks < 4; ++ks) sacc[kb] = vxb_mma_x3<X3>(ahf[ks], alf[ks], qfh[ks], qfl[ks], sacc[kb]);
         }
         __builtin_amdgcn_s_setprio(0);
         // the V^T fragments of the whole tile are requested here, before the softmax arithmetic that does not depend on them: their
@@ -199,8 +151,8 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
 #pragma unroll
                     for (int rr = 0; rr < 2; ++rr) {            // second read: keys + 8
                         const u16* ad = vt + vlane[db] + (kb * 32 + 16 * ks + 8 * rr) * 64;
-                        vaf[kb][ks][db][rr] = fd_tr16(ad);
-                        if (X3) vlf[kb][ks][db][rr] = fd_tr16(ad + TILE);
+                        vaf[kb][ks][db][rr] = vxb_tr16(ad);
+                        if (X3) vlf[kb][ks][db][rr] = vxb_tr16(ad + TILE);
                     }
         __builtin_amdgcn_sched_barrier(0);
         const int kbase_t = kt * BKV;
@@ -232,11 +184,11 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
                 psum += p0 + p1;
                 if (DROP) {
                     const unsigned key = (unsigned)(kbase_t + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi);
-                    const unsigned hsh = fd_keep_pair(g.seed, row_id, key >> 1);
+                    const unsigned hsh = vxb_drop_keep_pair(g.seed, row_id, key >> 1);
                     p0 = (hsh & 0xffffu) >= thr ? p0 * keep_scale : 0.f;
                     p1 = (hsh >> 16) >= thr ? p1 * keep_scale : 0.f;
                 }
-                if (X3) fd_split2(p0, p1, pbh[kb][r >> 1], pbl[kb][r >> 1]);
+                if (X3) vxb_split2(p0, p1, pbh[kb][r >> 1], pbl[kb][r >> 1]);
                 else pbh[kb][r >> 1] = vxb_pack_bf16(p0, p1);
             }
         l_run = l_run * alpha + psum;
@@ -249,13 +201,13 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_dl_kernel(FdArgs g) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 pfh = fd_from4(&pbh[kb][4 * ks]);
-                const bf16x8 pfl = X3 ? fd_from4(&pbl[kb][4 * ks]) : pfh;
+                const bf16x8 pfh = vxb_from4(&pbh[kb][4 * ks]);
+                const bf16x8 pfl = X3 ? vxb_from4(&pbl[kb][4 * ks]) : pfh;
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const bf16x8 vfh = fd_join(vaf[kb][ks][db][0], vaf[kb][ks][db][1]);
-                    const bf16x8 vfl = X3 ? fd_join(vlf[kb][ks][db][0], vlf[kb][ks][db][1]) : vfh;
-                    oacc[db] = fd_mma<X3>(vfh, vfl, pfh, pfl, oacc[db]);
+                    const bf16x8 vfh = vxb_join(vaf[kb][ks][db][0], vaf[kb][ks][db][1]);
+                    const bf16x8 vfl = X3 ? vxb_join(vlf[kb][ks][db][0], vlf[kb][ks][db][1]) : vfh;
+                    oacc[db] = vxb_mma_x3<X3>(vfh, vfl, pfh, pfl, oacc[db]);
                 }
             }
     }

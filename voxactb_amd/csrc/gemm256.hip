@@ -15,12 +15,9 @@
 //   * the direct loads of k-tile t + 1 are issued right after the barrier that opens k-tile t and have all of its
 //     48 MFMAs per wave to land (one barrier and one s_waitcnt vmcnt(0) per k-tile).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int BM = 256, BN = 256, BK = 32;
 constexpr int PTILE = BM * BK;                 // u16 per operand plane tile (16 KB)
@@ -39,11 +36,6 @@ struct G256Args {
     float slope;
     int accumulate;
 };
-
-__device__ __forceinline__ void g256_load16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 template <int X3>
 __global__ void __launch_bounds__(512, 1) gemm256_kernel(G256Args g) {
@@ -83,8 +75,8 @@ __global__ void __launch_bounds__(512, 1) gemm256_kernel(G256Args g) {
         for (int p = 0; p < NPL; ++p)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                g256_load16(g.A + p * g.a_plane + a_off[i] + k0, sb + p * PTILE + (2 * wid + i) * 512);
-                g256_load16(g.W + p * g.w_plane + w_off[i] + k0, sb + (NPL + p) * PTILE + (2 * wid + i) * 512);
+                vxb_load_lds16(g.A + p * g.a_plane + a_off[i] + k0, sb + p * PTILE + (2 * wid + i) * 512);
+                vxb_load_lds16(g.W + p * g.w_plane + w_off[i] + k0, sb + (NPL + p) * PTILE + (2 * wid + i) * 512);
             }
     };
 

@@ -15,11 +15,10 @@
 // ds_read_b32 per lane (lane l: A[m = l&31][k = l>>5]).  Global loads of tile t+1 are issued into
 // registers before the MFMAs of tile t (register double buffering), one barrier pair per tile.
 #include "common.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 16;
 
@@ -526,9 +525,6 @@ extern "C" int vxb_conv3d_wgrad_f32(const float* src0, const float* src1, int C0
 // the k-permutation inside one instruction cancels in the dot product.
 // =====================================================================================================================
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
     // round-to-nearest-even fp32 -> bf16, two values per dword

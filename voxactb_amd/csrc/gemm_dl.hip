@@ -13,12 +13,9 @@
 // swizzle makes the fragment reads (ds_read_b128, 32 rows x one chunk per half-wave) conflict-free without padding --
 // the swizzle is applied on the SOURCE side (which global chunk a lane fetches), since the destination is fixed.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int DL_A_KCONTIG = 0, DL_A_CONV = 1;
 constexpr int DTILE = 128 * 32;            // u16 per operand plane tile (8 KB)
@@ -45,11 +42,6 @@ struct DlArgs {
     unsigned d2s_magic;      // floor(2^32 / d2s_G) + 1 when M * d2s_G < 2^32 (exact multiply-high division), else 0
     const int* d2s_perm;     // d2s: column block p holds fine-grid phase d2s_perm[p] (nullptr = identity)
 };
-
-__device__ __forceinline__ void dl_load16(const u16* src, u16* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // BD: the B (weight) fragments come straight from global memory in fragment order, one k-tile ahead in two alternating
 // register sets -- no weight traffic through LDS.  With both operands in LDS the 2x2-tile waves of the x3 kernel need
@@ -159,8 +151,8 @@ __global__ void __launch_bounds__(256, 2) gemm_dl_kernel(DlArgs g) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const u16* s = asrc[i] ? asrc[i] + p * g.a_plane : g.zeros;
-                dl_load16(s, sb + p * DTILE + (2 * wid + i) * 512);
-                if (!BD) dl_load16(g.Bw + p * g.b_plane + b_off[i] + k0, sb + (NPL + p) * DTILE + (2 * wid + i) * 512);
+                vxb_load_lds16(s, sb + p * DTILE + (2 * wid + i) * 512);
+                if (!BD) vxb_load_lds16(g.Bw + p * g.b_plane + b_off[i] + k0, sb + (NPL + p) * DTILE + (2 * wid + i) * 512);
             }
         }
     };

@@ -17,12 +17,9 @@
 // Per output element the products are accumulated in the same order as in gemm_bf16_kernel (k ascending; lo*hi, hi*lo, hi*hi per
 // 16-deep step), so the results are bit-identical to the kernel this replaces.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int WBM = 128, WBK = 32, WLD = 40;       // rows per workgroup, k per tile, u16 per LDS row (32 + 8 pad: conflict-free b128 reads)
 
@@ -59,10 +56,9 @@ struct GwArgs {
     u16* aux16 = nullptr;    // plain epilogue, optional: the result also as ONE fp16 plane [M][N] (saturating RNE: the bits of vxb_split_f16_f32 on C)
 };
 
-typedef _Float16 gw_f16x8 __attribute__((ext_vector_type(8)));
 template <int X2>
 __device__ __forceinline__ f32x16 gw_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    if (X2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gw_f16x8, a), __builtin_bit_cast(gw_f16x8, b), c, 0, 0, 0);
+    if (X2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 

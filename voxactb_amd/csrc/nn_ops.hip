@@ -893,9 +893,6 @@ extern "C" int vxb_lrelu_bwd_act_f32(const float* dy, const float* y, float* dx,
     VXB_CHECK_LAUNCH();
     return VXB_OK;
 }
-extern "C" int vxb_lrelu_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, float slope, vxb_stream_t stream) {
-    return vxb_lrelu_bwd_act_f32(dy, y, dx, n, VXB_ACT_LRELU, slope, stream);
-}
 extern "C" int vxb_axpy_f32(float* dst, const float* src, int64_t n, float alpha, vxb_stream_t stream) {
     if (!dst || !src || n < 1) return VXB_EARG;
     hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dst, src, (long long)n, alpha);

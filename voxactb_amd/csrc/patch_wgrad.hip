@@ -5,7 +5,7 @@
 // gradient.  The voxel grid is a detached input (agent :100), so d(d0) feeds NOTHING but dW_in [64][10] and db_in [64] -- and those
 // are linear in d(d0):   dW_in[c][j] = sum_v lrelu'(d0[v][c]) * d(d0)[v][c] * vox[v][j].
 // The patchify term used to travel as a tensor: a 1^3 GEMM with 8000 output columns wrote it on the padded 105^3 grid (4.7 GB, 1.7 ms)
-// and vxb_pointwise_wgrad_ss3d_f32 gathered it back through the padding adjoint (4.7 of its 13.6 GB).  With non-overlapping patches
+// and vxb_pointwise_wgrad_ss3d_act_f32 gathered it back through the padding adjoint (4.7 of its 13.6 GB).  With non-overlapping patches
 // every (patch p, tap t) pair is ONE voxel v = clamp(5 p + t - 2) (the replicate padding's adjoint is that clamp), so the term is
 //     sum over (p, t) of  lrelu'(d0[v][c]) * G[p][t][c] * vox[v][j],      G[p][t][c] = sum_k dpatch[p][k] * Wp[k][c][t],
 // and G never needs to exist outside registers: a workgroup owns one tap (its 64 x 64 weight slice stays in registers as MFMA B
@@ -25,12 +25,9 @@
 // Single fp16 products like every weight gradient (a leaf), dpatch under the same device-side scale.  3.13 -> 1.32 ms per step for
 // the two gradients together (round 4: 1.84 + 1.29).
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int PCIN = 10;             // channels of the voxel grid
 
@@ -330,11 +327,4 @@ extern "C" int vxb_patch_dgrad_input_wgrad_act_f32(const float* dpatch, const vo
         hipLaunchKernelGGL(patch_wgrad_weight_finish_kernel, dim3(vxb_cdiv((long long)k * k * k * 4096, 256)), dim3(256), 0, st, ws_wp, k * k * k, nsplit,
                            scale, dWp);
     return vxb_wgin_finish_launch(ws, k * k * k * nsplit, scale, dW, db, st);
-}
-
-// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
-extern "C" int vxb_patch_dgrad_input_wgrad_f32(const float* dpatch, const void* wt_f16, const float* d0, const float* vox, int B, int V,
-                                               int G, int k, int pad, float slope, const float* scale, float* ws, int nsplit,
-                                               float* dW, float* db, float* dWp, float* ws_wp, vxb_stream_t stream) {
-    return vxb_patch_dgrad_input_wgrad_act_f32(dpatch, wt_f16, d0, vox, B, V, G, k, pad, VXB_ACT_LRELU, slope, scale, ws, nsplit, dW, db, dWp, ws_wp, stream);
 }

@@ -1307,7 +1307,7 @@ extern "C" int vxb_pointwise_ss3d_fwd_act_f32(const float* x, const float* W, co
 // part_ws: B * ceil(S^3 / 4096) * (64*Cin + 64) floats.  dW [64][Cin] and db [64] are ACCUMULATED.  Cin = 10 (the network's
 // voxel features: 3 + 3 + 3 + 1) -- other widths return VXB_ESIZE and the caller uses the two separate kernels.
 // fold_src (or null): [B, Sp^3, 64], a data gradient on the replicate-padded domain (S + 2 pad valid per axis) whose padding
-// adjoint (vxb_fold_pad_f32) is gathered and added to dy on the fly as well.
+// adjoint (vxb_fold_pad_act_f32) is gathered and added to dy on the fly as well.
 extern "C" int vxb_pointwise_wgrad_ss3d_act_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
                                             int S, int Cin, int Cout, int act, float slope, const float* lin, const float* stats,
                                             const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
@@ -1501,39 +1501,4 @@ extern "C" int vxb_se3_points_f32(const float* src, float* dst, const float* xf,
     hipLaunchKernelGGL(se3_points_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, src, dst, xf, (long long)n);
     VXB_CHECK_LAUNCH();
     return VXB_OK;
-}
-
-// the entries of ABI 4 and earlier: LeakyReLU(slope) as activation code 1 of the *_act_f32 entries above
-extern "C" int vxb_pointwise_fwd_f32(const float* x, const float* W, const float* bias, float* y, int64_t nvox, int Cin,
-                                     int Cout, float slope, vxb_stream_t stream) {
-    return vxb_pointwise_fwd_act_f32(x, W, bias, y, nvox, Cin, Cout, VXB_ACT_LRELU, slope, stream);
-}
-extern "C" int vxb_pointwise_wgrad_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws,
-                                       int64_t nvox, int Cin, int Cout, float slope, vxb_stream_t stream) {
-    return vxb_pointwise_wgrad_act_f32(x, y, dy, dW, db, part_ws, nvox, Cin, Cout, VXB_ACT_LRELU, slope, stream);
-}
-extern "C" int vxb_pointwise_ss3d_fwd_f32(const float* x, const float* W, const float* bias, float* y, int B, int S, int Cin, int Cout,
-                                          float slope, const float* lin, float* part_ws, float* out_ss, float* out_max, float* stats,
-                                          int32_t* argmax, vxb_stream_t stream) {
-    return vxb_pointwise_ss3d_fwd_act_f32(x, W, bias, y, B, S, Cin, Cout, VXB_ACT_LRELU, slope, lin, part_ws, out_ss, out_max, stats, argmax, stream);
-}
-extern "C" int vxb_pointwise_wgrad_ss3d_f32(const float* x, const float* y, const float* dy, float* dW, float* db, float* part_ws, int B,
-                                            int S, int Cin, int Cout, float slope, const float* lin, const float* stats,
-                                            const float* out_ss, const int32_t* argmax, const float* g_ss, const float* g_max,
-                                            const float* fold_src, int Sp, int pad, vxb_stream_t stream) {
-    return vxb_pointwise_wgrad_ss3d_act_f32(x, y, dy, dW, db, part_ws, B, S, Cin, Cout, VXB_ACT_LRELU, slope, lin, stats, out_ss, argmax, g_ss, g_max, fold_src, Sp, pad, stream);
-}
-extern "C" int vxb_conv3_c1_dgrad_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                                      int accumulate, int apply_lrelu_mask, float slope, vxb_stream_t stream) {
-    return vxb_conv3_c1_dgrad_act_f32(dq, w, u, du, B, S, C, accumulate, apply_lrelu_mask, VXB_ACT_LRELU, slope, stream);
-}
-extern "C" int vxb_conv3_c1_dgrad_ss3d_f32(const float* dq, const float* w, const float* u, float* du, int B, int S, int C,
-                                           int accumulate, float slope, const float* lin, const float* stats, const float* out_ss,
-                                           const int32_t* argmax, const float* g_ss, const float* g_max, float* dbias,
-                                           float* part_ws, float* du_scale, vxb_stream_t stream) {
-    return vxb_conv3_c1_dgrad_ss3d_act_f32(dq, w, u, du, B, S, C, accumulate, VXB_ACT_LRELU, slope, lin, stats, out_ss, argmax, g_ss, g_max, dbias, part_ws, du_scale, stream);
-}
-extern "C" int vxb_fold_pad_f32(const float* src, int Sp, int Cs, int c0, float* dst, const float* lrelu_of, int B, int S,
-                                int C, int pad, int accumulate, float slope, vxb_stream_t stream) {
-    return vxb_fold_pad_act_f32(src, Sp, Cs, c0, dst, lrelu_of, B, S, C, pad, accumulate, VXB_ACT_LRELU, slope, stream);
 }

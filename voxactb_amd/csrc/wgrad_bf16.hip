@@ -8,13 +8,9 @@
 // hands lane i channel c0 + i at positions p0 .. p0+3: a [4 pos][16 ch] block, transposed for free.
 // LDS row strides are = 16 (mod 64) dwords, which makes the 32 lanes served per LDS cycle hit 64 distinct banks.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 struct WgArgs {
     const float* src0;
@@ -370,12 +366,6 @@ __global__ void __launch_bounds__(256) wgrad_bf16_kernel(WgArgs g) {
 // tile t+1 is converted and stored into the other stage while tile t is multiplied, the global loads of tile t+2 are issued before
 // that, and there is ONE barrier per tile; the transposed fragment reads go through the compiler builtin (immediate offsets, waits
 // placed by the compiler).  Same tile shape, same operand rounding, same accumulation order as the generic kernel: bit-identical.
-typedef short wl_v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned long long wl_tr16(const u16* p) {
-    union { wl_v4s v; unsigned long long u; } t;
-    t.v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wl_v4s*)p);
-    return t.u;
-}
 
 template <int BN>
 __global__ void __launch_bounds__(256) wgrad_lin_f16_kernel(WgArgs g) {
@@ -491,13 +481,13 @@ __global__ void __launch_bounds__(256) wgrad_lin_f16_kernel(WgArgs g) {
             union { unsigned long long u[2]; bf16x8 v; } fa[TM], fb[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                fa[i].u[0] = wl_tr16(at + (kk + 0) * LDA + i * 32);
-                fa[i].u[1] = wl_tr16(at + (kk + 4) * LDA + i * 32);
+                fa[i].u[0] = vxb_tr16(at + (kk + 0) * LDA + i * 32);
+                fa[i].u[1] = vxb_tr16(at + (kk + 4) * LDA + i * 32);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                fb[j].u[0] = wl_tr16(bt + (kk + 0) * LDB + j * 32);
-                fb[j].u[1] = wl_tr16(bt + (kk + 4) * LDB + j * 32);
+                fb[j].u[0] = vxb_tr16(bt + (kk + 0) * LDB + j * 32);
+                fb[j].u[1] = vxb_tr16(bt + (kk + 4) * LDB + j * 32);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -698,12 +688,12 @@ __global__ void __launch_bounds__(512) wgrad_wide_f16_kernel(WideArgs g) {
                 const u16* bt_ = Bs0 + cur_ * WP * LDB + ks * 16 * LDB + b_lane;                                     \
                 union { unsigned long long u[2]; bf16x8 v; } fa_[2], fb_[4];                                         \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                       \
-                    fa_[i].u[0] = wl_tr16(at_ + i * 32);                                                             \
-                    fa_[i].u[1] = wl_tr16(at_ + 4 * LDA + i * 32);                                                   \
+                    fa_[i].u[0] = vxb_tr16(at_ + i * 32);                                                             \
+                    fa_[i].u[1] = vxb_tr16(at_ + 4 * LDA + i * 32);                                                   \
                 }                                                                                                    \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
-                    fb_[j].u[0] = wl_tr16(bt_ + j * 32);                                                             \
-                    fb_[j].u[1] = wl_tr16(bt_ + 4 * LDB + j * 32);                                                   \
+                    fb_[j].u[0] = vxb_tr16(bt_ + j * 32);                                                             \
+                    fb_[j].u[1] = vxb_tr16(bt_ + 4 * LDB + j * 32);                                                   \
                 }                                                                                                    \
                 _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                         \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = wg_mfma<PM>(fa_[i].v, fb_[j].v, acc[i][j]); \
@@ -773,12 +763,12 @@ __global__ void __launch_bounds__(512) wgrad_wide_f16_kernel(WideArgs g) {
             const u16* bt_ = Bs0 + cur_ * WP * LDB + ks * 16 * LDB + b_lane;                                         \
             union { unsigned long long u[2]; bf16x8 v; } fa_[2], fb_[4];                                             \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                           \
-                fa_[i].u[0] = wl_tr16(at_ + i * 32);                                                                 \
-                fa_[i].u[1] = wl_tr16(at_ + 4 * LDA + i * 32);                                                       \
+                fa_[i].u[0] = vxb_tr16(at_ + i * 32);                                                                 \
+                fa_[i].u[1] = vxb_tr16(at_ + 4 * LDA + i * 32);                                                       \
             }                                                                                                        \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
-                fb_[j].u[0] = wl_tr16(bt_ + j * 32);                                                                 \
-                fb_[j].u[1] = wl_tr16(bt_ + 4 * LDB + j * 32);                                                       \
+                fb_[j].u[0] = vxb_tr16(bt_ + j * 32);                                                                 \
+                fb_[j].u[1] = vxb_tr16(bt_ + 4 * LDB + j * 32);                                                       \
             }                                                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
             WW_ABL_CVT_A(S1, ks, as_)                                                                                 \

@@ -16,15 +16,11 @@
 //   * the next tile's global loads are issued before the current tile's MFMAs (15 float4 per thread in flight) --
 //     there are no other global loads in the loop, so in-order retirement does not get in the way.
 #include "common.h"
+#include "device_prims.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
 // voxel tile WTD x WTH x 8 = 128 voxels: 2x8x8 or 4x4x8 (the host picks the one that wastes fewer voxels on the grid edge:
 // S = 100 -> 100x100x104 instead of 100x104x104, S = 20 -> 20x20x24 instead of 20x24x24)
@@ -77,13 +73,6 @@ template <int PM>
 __device__ __forceinline__ f32x4 wh_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
     if (PM == 2) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8 wh_frag(const u16* p0, const u16* p1) {
-    union { s16x4 s[2]; bf16x8 v; } u;
-    u.s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p0));
-    u.s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p1));
-    return u.v;
 }
 
 // NCH = 16-channel chunks per workgroup.  1: 4 waves, two workgroups per CU.  2: 8 waves = two 4-wave groups that own one
@@ -436,8 +425,8 @@ __global__ void __launch_bounds__(256 * NCH, NCH == 1 ? 2 : 1) wgrad_halo_kernel
             bf16x8 bh[4], bl[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                bh[j] = wh_frag(db0 + 16 * j, db1 + 16 * j);
-                if (X3) bl[j] = wh_frag(db0 + DPL + 16 * j, db1 + DPL + 16 * j);
+                bh[j] = vxb_frag(db0 + 16 * j, db1 + 16 * j);
+                if (X3) bl[j] = vxb_frag(db0 + DPL + 16 * j, db1 + DPL + 16 * j);
             }
             // The A fragments of tap ti+1 are read while the MFMAs of tap ti run (a wave's slot past the end re-reads the last
             // active tap and its accumulator is never stored): the hi fragment into a second register set before the tap's
@@ -445,19 +434,19 @@ __global__ void __launch_bounds__(256 * NCH, NCH == 1 ? 2 : 1) wgrad_halo_kernel
             // -- 12 / 8 MFMAs of cover for the LDS round trip at 4 extra VGPRs (a full second set of both does not fit in 256
             // without spilling; without the barriers the scheduler sinks the reads below the MFMAs and every tap starts on
             // s_waitcnt lgkmcnt(0)).
-            bf16x8 ah = wh_frag(xa0 + toffs[0], xa1 + toffs[0]);
-            bf16x8 al = X3 ? wh_frag(xa0 + XPL + toffs[0], xa1 + XPL + toffs[0]) : ah;
+            bf16x8 ah = vxb_frag(xa0 + toffs[0], xa1 + toffs[0]);
+            bf16x8 al = X3 ? vxb_frag(xa0 + XPL + toffs[0], xa1 + XPL + toffs[0]) : ah;
 #pragma unroll
             for (int ti = 0; ti < 7; ++ti) {
                 if (ti >= nti) break;    // uniform: a phase with 8 / 12 / 18 active taps runs 2 / 3 / 5 slots
                 bf16x8 ahn = ah;
-                if (ti + 1 < 7) ahn = wh_frag(xa0 + toffs[ti + 1], xa1 + toffs[ti + 1]);
+                if (ti + 1 < 7) ahn = vxb_frag(xa0 + toffs[ti + 1], xa1 + toffs[ti + 1]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (X3) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[ti][j] = wh_mfma<PM>(al, bh[j], acc[ti][j]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ti + 1 < 7) al = wh_frag(xa0 + XPL + toffs[ti + 1], xa1 + XPL + toffs[ti + 1]);
+                    if (ti + 1 < 7) al = vxb_frag(xa0 + XPL + toffs[ti + 1], xa1 + XPL + toffs[ti + 1]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[ti][j] = wh_mfma<PM>(ah, bl[j], acc[ti][j]);

@@ -1199,7 +1199,7 @@ PATCH_WGRAD_WEIGHT = os.environ.get('VOXACTB_PATCH_WGRAD_WEIGHT', '1') != '0'   
 
 def patch_dgrad_input_wgrad(dpatch, Wp, d0, vox, dW, db, B, V, G, k, pad, dWp=None, act=LRELU):
     """dW [64][10] += / db [64] += the patchify data gradient's share of the input conv's weight / bias gradient, straight from
-    dpatch [B, G^3, 64] (patch_wgrad.hip: vxb_patch_dgrad_input_wgrad_f32) -- the 4.7 GB data gradient tensor and its padding
+    dpatch [B, G^3, 64] (patch_wgrad.hip: vxb_patch_dgrad_input_wgrad_act_f32) -- the 4.7 GB data gradient tensor and its padding
     adjoint are never formed.  dWp (the patchify weight's gradient tensor [64][64][k][k][k], contiguous): += the patchify conv's own
     weight gradient from the same pass over d0."""
     wt = Wp.reshape(Wp.shape[0], Wp.shape[1], k ** 3).permute(2, 1, 0).contiguous().to(torch.float16)      # [tap][c][kout]
